@@ -16,12 +16,17 @@ projections of every decoder layer targeted.  Per step, on every rank:
 
 value = non-padding tokens of all ranks' micro-batches / step time (max over ranks); per-GPU
 work is fixed as N grows ("weak").  The base model's own linears / attention are not part of
-this path and are not run.  Extras on the line: the dW aggregate+merge time per
-step (the metric's second half), the live roofline of the dominant kernel, the reference
-algorithm's CPU baseline, and the reference torch path on the same GPU.
+this path and are not run.  A plain run sets up, warms up, times the K steps and
+prints the line: the headline figures, the dW aggregate+merge time per step (the metric's second
+half) and the host-side cost of the timed steps.  `--full` adds every measurement that takes runs
+of its own: the live roofline of the dominant kernel (a second, instrumented pass over the same
+micro-batches), the other exchange strategy's dW path, the reference torch path on the same GPU,
+the dW path of an emulated wider run, and the reference algorithm's CPU baseline.
+`--dump-outputs DIR` writes what the last timed step left behind (merged weights, Adam state) as
+DIR/<name>.npy, so that two builds can be compared output for output.
 
   python bench.py [--gpus N --steps K --warmup W] [--workload llama2-7b|qproj|mistral-7b|
-                  llama2-13b|qwen2.5-0.5b] [--exchange gather|allreduce]
+                  llama2-13b|qwen2.5-0.5b] [--exchange gather|allreduce] [--full] [--dump-outputs DIR]
   N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
          or plainly `python bench.py --gpus N`: without WORLD_SIZE in the environment the bench starts
          the N ranks itself (a torch.distributed.run child, before this process touches the GPU) and
@@ -500,6 +505,49 @@ class _HostPlatform:
         return {}
 
 
+DUMP_PER_MODULE = 8192   # sampled entries of every module's merged weight
+DUMP_PER_ARENA = 1 << 20  # sampled entries of each flat Adam buffer
+
+
+def _sample_index(n, k, seed):
+    """k fixed, seeded positions in [0, n); every position, in order, if n <= k."""
+    if n <= k:
+        return torch.arange(n)
+    g = torch.Generator()
+    g.manual_seed(seed)
+    return torch.randint(0, n, (k,), generator=g)
+
+
+class OutputSampler:
+    """--dump-outputs: what a caller of the timed path holds after a step -- every module's merged
+    weight W_res and the factor arena's Adam state (m, v, this step's delta; the gradients are
+    zeroed by the step) -- at fixed, seeded positions (DUMP_PER_MODULE per module, DUMP_PER_ARENA
+    per arena buffer: at most ~40 MB for the largest workload).  The same positions of W_res are
+    read once before the first step, so the accumulated update W_res - W_0 is written too: at the
+    bench's learning rates it is 1e-4 of W and would drown in a comparison of W_res alone."""
+
+    def __init__(self, layers, device):
+        self.layers = layers
+        self.widx = [_sample_index(L.W_res.numel(), DUMP_PER_MODULE, zlib.crc32(L.name.encode())).to(device)
+                     for L in layers]
+        self.arenas = list({id(L._arena): L._arena for L in layers}.values())
+        self.aidx = [_sample_index(a.F, DUMP_PER_ARENA, 7 + i).to(device) for i, a in enumerate(self.arenas)]
+        self.w_start = self._weights()
+
+    def _weights(self):
+        return torch.cat([L.W_res.reshape(-1)[i].double() for L, i in zip(self.layers, self.widx)]).cpu().numpy()
+
+    def write(self, outdir):
+        os.makedirs(outdir, exist_ok=True)
+        w = self._weights()
+        arrays = {"w_res": w.astype(np.float32), "w_update": w - self.w_start}
+        for name in ("m", "v", "delta"):
+            arrays["adam_" + name] = torch.cat([getattr(a, name)[i] for a, i in zip(self.arenas, self.aidx)]
+                                               ).float().cpu().numpy()
+        for name, arr in arrays.items():
+            np.save(os.path.join(outdir, name + ".npy"), arr)
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -538,8 +586,15 @@ def main(argv=None, host_ops=None, return_state=False):
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--seq", type=int, default=512)
     ap.add_argument("--layers", type=int, default=None, help="override the workload's decoder-layer count (experiments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ref-torch", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every measurement that takes runs of its own: the "
+                         "instrumented per-kernel pass (roofline), the other exchange strategy, the reference torch "
+                         "path, the emulated wider run and the CPU baseline (each with its own --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step left (sampled merged weights and their accumulated update, "
+                         "Adam m / v / delta) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-ref-torch", action="store_true", help="--full: skip the reference torch path")
     ap.add_argument("--init", default="svd", choices=["svd", "random"],
                     help="svd: the K1 SVD-slice init (default); random: random factors (PMC profiling runs only: "
                          "the counters of thousands of rocSOLVER launches would dominate the profile)")
@@ -554,6 +609,8 @@ def main(argv=None, host_ops=None, return_state=False):
                     help="N=1 only: also time the dW path of a WN-GPU run (rank loop of WN segments) for "
                          "this build and the reference torch path (exchange excluded from both)")
     args = ap.parse_args(argv)
+    if args.timing_out and not args.full:
+        ap.error("--timing-out records the instrumented pass: run with --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and host_ops is None:
         # no launcher: start the ranks as a child before anything here touches the GPU
@@ -662,6 +719,7 @@ def main(argv=None, host_ops=None, return_state=False):
             host_parts["flush"] += h2 - h1
             host_parts["step"] += h3 - h2
 
+    sampler = OutputSampler(layers, device) if args.dump_outputs and rank == 0 else None
     for _ in range(args.warmup):
         one_step(False)
     plat.sync()
@@ -687,30 +745,34 @@ def main(argv=None, host_ops=None, return_state=False):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     timed_mb = toks[args.warmup * args.micro:]
-    # The per-kernel HIP-event timing (roofline) brackets every launch with two events: on a
-    # launch-bound stretch that host work would stall the GPU, so it runs in a second,
-    # identical timed region (same micro-batch lengths) instead of inside the one `value` uses.
     blocked_ms = wait_us(1) / 1e3  # host time spent waiting for the GPU (staging-ring back-pressure)
-    dw_value = list(dw_ms)
-    host_value = host_s[0]
-    parts_value = dict(host_parts)
-    dw_ms.clear()
-    mb_it[0] = iter(timed_mb)
-    kernel_timing(enable=True, reset=True)
-    ti0 = time.perf_counter()
-    for _ in range(args.steps):
-        one_step(True)
-    plat.sync()
-    instrumented_ms = 1e3 * (time.perf_counter() - ti0) / args.steps
-    ks = kernel_timing(enable=False)
-    dw_ms[:] = dw_value
-    host_s[0] = host_value
-    host_parts.update(parts_value)
-    if args.timing_out and rank == 0:
-        with open(args.timing_out, "w") as f:
-            json.dump(ks, f)
+    if sampler is not None:  # the last timed step's outputs, before --full steps the model further
+        sampler.write(args.dump_outputs)
+    ks, instrumented_ms = {}, None
+    if args.full:
+        # The per-kernel HIP-event timing (roofline) brackets every launch with two events: on a
+        # launch-bound stretch that host work would stall the GPU, so it runs in a second,
+        # identical timed region (same micro-batch lengths) instead of inside the one `value` uses.
+        dw_value = list(dw_ms)
+        host_value = host_s[0]
+        parts_value = dict(host_parts)
+        dw_ms.clear()
+        mb_it[0] = iter(timed_mb)
+        kernel_timing(enable=True, reset=True)
+        ti0 = time.perf_counter()
+        for _ in range(args.steps):
+            one_step(True)
+        plat.sync()
+        instrumented_ms = 1e3 * (time.perf_counter() - ti0) / args.steps
+        ks = kernel_timing(enable=False)
+        dw_ms[:] = dw_value
+        host_s[0] = host_value
+        host_parts.update(parts_value)
+        if args.timing_out and rank == 0:
+            with open(args.timing_out, "w") as f:
+                json.dump(ks, f)
     legs = None
-    if world == 1 and not args.no_other_exchange and host_ops is None:
+    if args.full and world == 1 and not args.no_other_exchange and host_ops is None:
         # the other exchange strategy's dW path on the same arena (north-star contract: K4 store ->
         # all-reduce (identity at N = 1) -> K5 merge; or the fused gather-merge K4)
         other = "allreduce" if args.exchange == "gather" else "gather"
@@ -801,7 +863,6 @@ def main(argv=None, host_ops=None, return_state=False):
         # because it had run 64 probe groups (8 steps) ahead of the GPU
         "host_blocked_ms_per_step": round(blocked_ms / args.steps, 3),
         "host_busy_ms_per_step": round(1e3 * host_s[0] / args.steps - blocked_ms / args.steps, 3),
-        "instrumented_ms_per_step": round(instrumented_ms, 3),
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -816,10 +877,12 @@ def main(argv=None, host_ops=None, return_state=False):
         "init_s": round(t_svd, 2),
         "init": args.init,
     }
+    if instrumented_ms is not None:
+        res["instrumented_ms_per_step"] = round(instrumented_ms, 3)
     if legs is not None:
         legs[args.exchange]["dw_ms_per_step"] = round(dw, 3)
         res["exchange_legs"] = legs
-    if not args.no_ref_torch and host_ops is None:
+    if args.full and not args.no_ref_torch and host_ops is None:
         try:
             ref = ref_torch_gpu(layers, Xs, Gs, rows_timed[:args.micro], world,
                                 sum(n for n, _ in timed_mb[:args.micro]), device, world=world)
@@ -830,7 +893,7 @@ def main(argv=None, host_ops=None, return_state=False):
             res["ref_torch_gpu"] = {"error": str(e)[:200]}
         if world == 1 and args.emulate_wn > 1:
             res["dw_emulated_wn"] = dw_emulated(layers, stepper, tops, args.emulate_wn, device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         T_mean = int(round(float(np.mean(rows_timed))))
         res["cpu_baseline"] = cpu_baseline(wl, args.micro, T_mean, tokens / args.steps / args.micro, world)
     if rank == 0:

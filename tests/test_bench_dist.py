@@ -113,6 +113,48 @@ def test_bench_self_launch_cpu(tmp_path):
     _check_line(json.loads(lines[0]), 2, "gather")
 
 
+def test_bench_plain_full_and_dump_cpu(tmp_path, monkeypatch, capsys):
+    """A plain run times its steps and prints the line, nothing else; --full adds the measurements that take
+    runs of their own; --dump-outputs writes the last timed step's outputs, identical from run to run and
+    untouched by the extra steps of --full (world size 1, CPU op set)."""
+    import numpy as np
+    for p in (HERE, ROOT):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    from cpu_ops import CpuOps
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    base = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--workload", "tiny-test", "--micro", "2", "--batch", "2",
+            "--seq", "48"]
+
+    def run(extra, out):
+        res = bench.main(base + ["--dump-outputs", str(tmp_path / out)] + extra, host_ops=CpuOps())
+        lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["value"] == res["value"]
+        return res, {f[:-4]: np.load(tmp_path / out / f) for f in sorted(os.listdir(tmp_path / out))}
+
+    plain, a = run([], "a")
+    _, b = run([], "b")
+    full, c = run(["--full"], "c")
+    _check_line(plain, 1, "gather")
+    _check_line(full, 1, "gather")
+    for k in ("instrumented_ms_per_step", "cpu_baseline", "ref_torch_gpu", "exchange_legs", "dw_emulated_wn"):
+        assert k not in plain, k
+    assert plain["roofline"] is None
+    assert full["instrumented_ms_per_step"] > 0 and full["cpu_baseline"]["value"] > 0
+    assert sorted(a) == ["adam_delta", "adam_m", "adam_v", "w_res", "w_update"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and v.size and np.isfinite(v).all(), k
+        np.testing.assert_allclose(b[k], v, rtol=1e-5, atol=1e-9, err_msg=k)
+        np.testing.assert_allclose(c[k], v, rtol=1e-5, atol=1e-9, err_msg=k)
+    # three optimizer steps moved the weights and left Adam state behind
+    assert np.abs(a["w_update"]).max() > 0 and np.abs(a["adam_m"]).max() > 0 and a["adam_v"].max() > 0
+    with pytest.raises(SystemExit):
+        bench.main(base + ["--timing-out", str(tmp_path / "t.json")], host_ops=CpuOps())
+
+
 def test_bench_rejects_mismatched_world(monkeypatch):
     """A launcher that sets WORLD_SIZE different from --gpus is an error (no silent re-launch)."""
     sys.path.insert(0, ROOT)

@@ -4,7 +4,7 @@
 set -u
 mkdir -p gpurun_out
 for g in "$@"; do
-  HDP_PROBE_GROUP=$g timeout -k 10 240 python bench.py --layers 8 --steps 5 --warmup 2 --no-cpu-baseline \
+  HDP_PROBE_GROUP=$g timeout -k 10 240 python bench.py --full --layers 8 --steps 5 --warmup 2 --no-cpu-baseline \
       --no-ref-torch --emulate-wn 1 > gpurun_out/ic_g$g.json 2> gpurun_out/ic_g$g.err || exit $?
   echo "group $g done"
 done

@@ -16,7 +16,7 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GR
   i=$((i+1))
   rm -rf /tmp/pmcb_$i
   timeout -s KILL 400 rocprofv3 --pmc $set --kernel-include-regex "hdp::" --output-format csv -d /tmp/pmcb_$i -o run -- \
-      python3 bench.py --steps 2 --warmup 1 --init random --no-cpu-baseline --no-ref-torch --emulate-wn 1 \
+      python3 bench.py --full --steps 2 --warmup 1 --init random --no-cpu-baseline --no-ref-torch --emulate-wn 1 \
       --no-other-exchange --timing-out $OUT/timing.json "$@" > $OUT/pass$i.log 2>&1 || exit $?
   find /tmp/pmcb_$i -name "*counter_collection.csv" -exec cp {} $OUT/pass$i.csv \;
   echo "pass $i done ($TAG)"

@@ -63,7 +63,7 @@ def main():
             fams[fam][i].append(ctr)
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from bench import kernel_source_digest  # noqa: E402
-    res = dict(source="tools/pmc_bench.sh: rocprofv3 --pmc over python3 bench.py --steps 2 --warmup 1 --init random "
+    res = dict(source="tools/pmc_bench.sh: rocprofv3 --pmc over python3 bench.py --full --steps 2 --warmup 1 --init random "
                       "--no-cpu-baseline --no-ref-torch --emulate-wn 1 --no-other-exchange",
                source_digest=kernel_source_digest(), args=open(os.path.join(src, "args.txt")).read().strip()
                if os.path.exists(os.path.join(src, "args.txt")) else "",
