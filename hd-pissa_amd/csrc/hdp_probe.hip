@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "hdp_probe_int.h"
+#include "hdp_probe_plan.h"
 
 namespace hdp {
 
@@ -428,7 +429,8 @@ __global__ __launch_bounds__(256) void probe_finish4_kernel(GroupArgs ga) {
 // PERSISTENT schedule: a launch has exactly G resident workgroups (occupancy x CUs, capped so
 // each gets >= kSwMinSteps steps); the U steps of the group, flattened as (module, stripe,
 // row step), are split into G equal contiguous ranges -- no tail quantization, one launch per
-// phase however large the group.  A workgroup's range crosses few stripes; OUTER accumulators
+// phase however large the group (plan_ranges, hdp_probe_plan.h; phase A of a float32 shared-X group cuts
+// ranges of equal COST instead, kSwWeightA).  A workgroup's range crosses few stripes; OUTER accumulators
 // live in registers over a stripe segment and are flushed as one piece per segment.
 //
 // Workgroup: 8 waves, each owning 64 columns of the stripe.  A lane loads 4 consecutive columns
@@ -670,20 +672,18 @@ struct SweepArgs {
   int* err;       // device error word (host-mapped): set when a hand-off wait gives up
   int* errd;      // its device-memory copy (set together): what K3 reads in stream order (L2, not PCIe)
   const SweepDesc* d;  // [n] this phase's module sides (device)
-  const int* wst;      // [3 G] where workgroup w starts: module, stripe, step (device; host-planned)
+  const int* wst;      // [4 G] where workgroup w starts: module, stripe, step, and how many workgroups before
+                       //       it hold earlier steps of that stripe (device; host-planned)
+  const int* bnd;      // [G + 1] first flattened step of every workgroup's range, bnd[G] = U (plan_ranges)
 };
 
-__device__ __forceinline__ int64_t sw_lo(int w, int64_t U, int G) { return (int64_t)w * U / G; }
-// the workgroup whose range holds step u: the largest w with sw_lo(w) <= u
-__device__ __forceinline__ int sw_owner(int64_t u, int64_t U, int G) { return (int)(((u + 1) * G - 1) / U); }
-
 // one stripe segment: steps [s0, s0 + n) of stripe ct of d.  `i0` = the workgroup's step count
-// before it (parity of the PROJ reduction buffer).  Steps whose 16 rows are all < T run a
+// before it (parity of the PROJ reduction buffer); `piece` = the segments of the stripe before this one.  Steps whose 16 rows are all < T run a
 // pipelined loop on incremented pointers; a final partial step (T % 16 != 0) is clamped.
 // OCC = resident workgroups per CU the kernel is built for: 1 (two steps of loads in flight,
 // three register sets) or 2 (one step in flight, two sets: <= 128 VGPRs, 16 waves per CU)
 template <int DT, int RB, int MODE, bool VEC, int OCC, bool FUSE, bool K32>
-__device__ __forceinline__ void sweep_segment(const SweepDesc& d, int ct, int s0, int n, int64_t i0, int w,
+__device__ __forceinline__ void sweep_segment(const SweepDesc& d, int ct, int s0, int n, int64_t i0, int piece,
                                               const SweepArgs& sa, float* tile, float* red, int* flags, int wave,
                                               int lane) {
   constexpr bool PROJ = (MODE & kSwProj) != 0, OUTER = (MODE & kSwOuter) != 0;
@@ -1252,10 +1252,8 @@ __device__ __forceinline__ void sweep_segment(const SweepDesc& d, int ct, int s0
   }
   if constexpr (OUTER) {  // flush this segment's piece
     HDP_MFMA_FENCE();
-    const int64_t u0 = d.pre + (int64_t)ct * d.S;
-    const int first = sw_owner(u0, sa.U, sa.G);
-    const int piece = w - first;
-    if (sw_owner(u0 + d.S - 1, sa.U, sa.G) == first) {  // the stripe's only segment: the gradient itself
+    // `piece` = this segment's place among the stripe's segments, which keep the workgroup order (host-planned)
+    if (s0 == 0 && n == d.S) {  // the stripe's only segment: the gradient itself
       if constexpr (FUSE) {
         if (col < N) sw_store_g_fuse(d, acc2, col, g, VEC);
       } else {
@@ -1304,7 +1302,7 @@ __global__ __launch_bounds__(512, OCC == 2 ? 4 : 2) void probe_sweep_kernel(Swee
   // LDS (PROJ): [staging 8 x 16 x kTileLd] [red kSwRedBufs x 8 x 16 x rp] [flags 2 x kSwRedBufs]
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int w = blockIdx.x;
-  const int64_t lo = sw_lo(w, sa.U, sa.G), nsteps = sw_lo(w + 1, sa.U, sa.G) - lo;
+  const int64_t nsteps = sa.bnd[w + 1] - sa.bnd[w];
   if (nsteps <= 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* tile = lds + wave * 16 * kTileLd;
@@ -1314,13 +1312,15 @@ __global__ __launch_bounds__(512, OCC == 2 ? 4 : 2) void probe_sweep_kernel(Swee
     if (threadIdx.x < 2 * sw_nbuf<RB, FUSE>()) flags[threadIdx.x] = 0;
     __syncthreads();
   }
-  int m = sa.wst[3 * w], ct = sa.wst[3 * w + 1], s = sa.wst[3 * w + 2];
+  int m = sa.wst[4 * w], ct = sa.wst[4 * w + 1], s = sa.wst[4 * w + 2];
+  int piece = sa.wst[4 * w + 3];  // of the first segment; the later ones begin their stripes
   for (int64_t done = 0; done < nsteps;) {  // stripe segments of this workgroup's range
     const SweepDesc d = sa.d[m];  // a register copy: the segment's stores cannot alias it
     const int n = (int)min((int64_t)(d.S - s), nsteps - done);
-    sweep_segment<DT, RB, MODE, VEC, OCC, FUSE, K32>(d, ct, s, n, done, w, sa, tile, red, flags, wave, lane);
+    sweep_segment<DT, RB, MODE, VEC, OCC, FUSE, K32>(d, ct, s, n, done, piece, sa, tile, red, flags, wave, lane);
     done += n;
     s = 0;
+    piece = 0;
     if (++ct == d.nct) {
       ct = 0;
       ++m;
@@ -1384,10 +1384,8 @@ struct FinDesc {
 };
 struct SwFinishArgs {
   int n, rp;
-  int64_t U[2];    // phase B / C total steps
-  int G[2];        // phase B / C workgroups
   const FinDesc* d;  // [n] (device)
-  const int* jobs;   // [njobs][2]: module, 2 stripe + side (1 = B side) -- the split stripes only
+  const int* jobs;   // [njobs][4]: module, 2 stripe + side (1 = B side), pieces, 0 -- the split stripes only
   int bx;            // workgroups per job
 };
 
@@ -1403,8 +1401,8 @@ __global__ __launch_bounds__(256) void probe_sweep_finish_kernel(SwFinishArgs fa
 #pragma clang fp contract(off)  // g + s*sum as two roundings, like autograd's mul then add
   typedef float vec __attribute__((ext_vector_type(V)));
   const int job = blockIdx.x / fa.bx;
-  const FinDesc& dm = fa.d[fa.jobs[2 * job]];
-  const int code = fa.jobs[2 * job + 1], ct = code >> 1;
+  const FinDesc& dm = fa.d[fa.jobs[4 * job]];
+  const int code = fa.jobs[4 * job + 1], ct = code >> 1;
   const bool sideA = (code & 1) == 0;
   const int r = dm.r;
   const int e = ((int)(blockIdx.x % fa.bx) * 256 + (int)threadIdx.x) * V;  // element of the r x kSwC job
@@ -1420,11 +1418,7 @@ __global__ __launch_bounds__(256) void probe_sweep_finish_kernel(SwFinishArgs fa
   const int64_t n = (int64_t)ct * kSwC + nn;
   if (n >= (sideA ? dm.in : dm.out)) return;
   const SwFinishSide& sd = sideA ? dm.sx : dm.sg;
-  const int64_t u0 = sd.pre + (int64_t)ct * sd.S;
-  const int64_t U = fa.U[sd.ph];
-  const int Gw = fa.G[sd.ph];
-  const int k0 = sw_owner(u0, U, Gw), np = sw_owner(u0 + sd.S - 1, U, Gw) - k0 + 1;
-  if (np == 1) return;  // one segment covered the stripe and wrote its gradient block itself
+  const int np = fa.jobs[4 * job + 2];  // workgroup ranges that meet the stripe (host: plan_owner), >= 2
   const float* p = sd.part + (int64_t)ct * sd.kmax * fa.rp * kSwC + (sideA ? (int64_t)j * kSwC + nn : (int64_t)nn * fa.rp + j);
   const int64_t stride = (int64_t)fa.rp * kSwC;
   vec s0 = 0.f, s1 = 0.f;
@@ -1442,7 +1436,8 @@ __global__ __launch_bounds__(256) void probe_sweep_finish_kernel(SwFinishArgs fa
 // Per-flush descriptor tables: one host blob copied to the head of the group's device workspace
 // in stream order.  The host side goes through a ring of pinned staging buffers, each reused only
 // after the copy that last read it has executed (its event).
-constexpr size_t kTableFixed = 3 * 4096 * 3 * sizeof(int) + 4096;  // WG start tables, up to 4096 WGs/phase
+// WG start tables (4 ints) and range boundaries (1 int, + the end) per phase, up to 4096 WGs/phase
+constexpr size_t kTableFixed = 3 * 4096 * 5 * sizeof(int) + 8192;
 constexpr size_t kTablePerModule = 3 * sizeof(SweepDesc) + 2 * sizeof(YRedDesc) + sizeof(FinDesc) + 64;
 
 // Device error word of the sweep's PROJ hand-off: pinned host memory mapped into the device, so the
@@ -1581,9 +1576,9 @@ static bool slice_r(int r, int b_transposed) {
 }
 static int n_slices(int r) { return (r + 63) / 64; }
 
-// the finish's job list (one int2 per split stripe) is part of the group's tables: room for every stripe
+// the finish's job list (one int4 per split stripe) is part of the group's tables: room for every stripe
 static size_t finish_jobs_bytes(int64_t in, int64_t out) {
-  return (size_t)(((in + kSwC - 1) / kSwC + (out + kSwC - 1) / kSwC) * 8 + 255) / 256 * 256;
+  return (size_t)(((in + kSwC - 1) / kSwC + (out + kSwC - 1) / kSwC) * 16 + 255) / 256 * 256;
 }
 
 static int sweep_kmax(int64_t T) { return (int)(((T + 15) / 16 + kSwMinSteps - 1) / kSwMinSteps) + 2; }
@@ -1727,16 +1722,44 @@ static int phase_grid(int64_t U, size_t lds) {
   return (int)(cap < 1 ? 1 : (cap < slots ? cap : slots));
 }
 
-// where workgroup w of G starts: (module, stripe, step) of flattened step w * U / G
-static void phase_starts(const std::vector<SweepDesc>& d, int64_t U, int G, int* out) {
+// Cost of one 16-row step of a side with nb r-blocks, relative to nb = 1 (x 64), in phase A of a float32
+// shared-X group (the FUSE X6 PROJ instance).  A step's MFMA and LDS work grows with nb while its bytes do
+// not, so the q/k/v sets (3 blocks) and gate/up (2) take longer per step than o_proj / down_proj (1); an
+// equal split of the steps left the light workgroups idle at the phase's end (LLaMA-2-7B group: 420 -> 370 us).
+// Measured per step on homogeneous groups at the LLaMA-2-7B shapes (tools/probe_weights.py):
+// profiles/r07_probe_weights.jsonl -- 1 : 1.15 : 1.37 : 1.54.  Phase C (f32 OUTER) measured 1 : 0.94 : 1.13 :
+// 1.49: its 3-block steps are not the 1.3 x that would explain its time, so it keeps the equal split.
+constexpr int kSwWeightA[kSwMaxBlk + 1] = {64, 64, 74, 88, 98};
+// env HDP_PROBE_BALANCE=0: the equal split w * U / G in every phase (A/B measurements, tests)
+static bool probe_balance() {
+  const char* e = getenv("HDP_PROBE_BALANCE");
+  return !(e && e[0] == '0');
+}
+
+// the ranges of one phase's workgroups (plan_ranges); weights = per-nb step costs, or null for equal steps
+static int phase_ranges(const std::vector<SweepDesc>& d, int G, const int* weights, std::vector<int64_t>& bounds) {
+  std::vector<PlanSide> sides(d.size());
+  for (size_t i = 0; i < d.size(); ++i) {
+    const int nb = d[i].nb < 1 ? 1 : d[i].nb > kSwMaxBlk ? kSwMaxBlk : d[i].nb;
+    sides[i] = PlanSide{d[i].pre, d[i].nct, d[i].S, weights ? weights[nb] : 1};
+  }
+  return plan_ranges(sides, G, kSwMinSteps, bounds);
+}
+
+// where workgroup w of G starts: (module, stripe, step) of flattened step bounds[w], and the workgroups before
+// it on that stripe (its first segment's piece index); bnd = the device's bounds
+static void phase_starts(const std::vector<SweepDesc>& d, const std::vector<int64_t>& bounds, int G, int* out,
+                         int* bnd) {
   int m = 0;
+  for (int w = 0; w <= G; ++w) bnd[w] = (int)bounds[w];
   for (int w = 0; w < G; ++w) {
-    const int64_t lo = (int64_t)w * U / G;
+    const int64_t lo = bounds[w];
     while (m + 1 < (int)d.size() && lo >= d[m + 1].pre) ++m;
     const int64_t rem = lo - d[m].pre;
-    out[3 * w] = m;
-    out[3 * w + 1] = (int)(rem / d[m].S);
-    out[3 * w + 2] = (int)(rem % d[m].S);
+    out[4 * w] = m;
+    out[4 * w + 1] = (int)(rem / d[m].S);
+    out[4 * w + 2] = (int)(rem % d[m].S);
+    out[4 * w + 3] = w - plan_owner(bounds, lo - rem % d[m].S);
   }
 }
 
@@ -1993,7 +2016,20 @@ static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
              : phase_grid<DT, RB, MODE_B, VEC, OCC_B>(U[1], proj_lds);
   HDP_CHECK_ARG(G[0] <= 4096 && G[1] <= 4096 && G[2] <= 4096, "probe sweep: grid above the table size");
   HDP_CHECK_ARG(yblk < 65536 && n < 65536, "probe sweep: group too large");
-  // finish: the pieces of X's OUTER and of G's (phase index 0 = B, 1 = C in fa.U / fa.G); every
+  // the workgroups' ranges: cost-weighted in phase A of a float32 shared-X group, equal steps elsewhere
+  std::vector<int64_t> bounds[3];
+  const bool weighted = fuse && !BF && probe_balance();
+  for (int ph = 0; ph < 3; ++ph) {
+    HDP_CHECK_ARG(U[ph] < (1ll << 31), "probe sweep: too many steps in one phase");
+    G[ph] = phase_ranges(sd[ph], G[ph], weighted && ph == 0 ? kSwWeightA : nullptr, bounds[ph]);
+    // memory safety: a stripe's piece buffer holds sweep_kmax pieces, which is what ranges of >= kSwMinSteps
+    // steps can produce (a single workgroup may hold fewer: one piece per stripe)
+    const int64_t least = U[ph] < kSwMinSteps ? U[ph] : kSwMinSteps;
+    bool ok = (int)bounds[ph].size() == G[ph] + 1 && bounds[ph][0] == 0 && bounds[ph][G[ph]] == U[ph];
+    for (int w = 0; ok && w < G[ph]; ++w) ok = bounds[ph][w + 1] - bounds[ph][w] >= least;
+    HDP_CHECK_ARG(ok, "probe sweep: a workgroup range below the minimum step count");
+  }
+  // finish: the pieces of X's OUTER and of G's (SwFinishSide::ph 0 = phase B, 1 = C); every
   // module's pieces are in its own part buffers (a shared-X set's OUTER writes each member's rows there)
   for (int i = 0; i < n; ++i) {
     const ProbeDesc& p = ga.d[i];
@@ -2003,12 +2039,13 @@ static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
     fd[i].sx = SwFinishSide{p.partA, dx.pre, dx.S, dx.kmax, x_in_c ? 1 : 0, 0};
     fd[i].sg = SwFinishSide{p.partB, dg.pre, dg.S, dg.kmax, g_in_c ? 1 : 0, 0};
   }
-  // one blob: [sd A | sd B | sd C | wst A | wst B | wst C | yd R1 | yd R2 | fd]
+  // one blob: [sd A | sd B | sd C | wst A | wst B | wst C | bnd A | bnd B | bnd C | yd R1 | yd R2 | fd]
   size_t off = 0;
   auto place = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  size_t o_sd[3], o_w[3], o_y[2];
+  size_t o_sd[3], o_w[3], o_b[3], o_y[2];
   for (int ph = 0; ph < 3; ++ph) o_sd[ph] = place(sizeof(SweepDesc) * sd[ph].size());
-  for (int ph = 0; ph < 3; ++ph) o_w[ph] = place(sizeof(int) * 3 * G[ph]);
+  for (int ph = 0; ph < 3; ++ph) o_w[ph] = place(sizeof(int) * 4 * G[ph]);
+  for (int ph = 0; ph < 3; ++ph) o_b[ph] = place(sizeof(int) * (G[ph] + 1));
   for (int k = 0; k < 2; ++k) o_y[k] = place(sizeof(YRedDesc) * n);
   const size_t o_f = place(sizeof(FinDesc) * n);
   // the finish's jobs: the stripes that more than one workgroup segment covered (the others wrote their
@@ -2016,7 +2053,6 @@ static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
   std::vector<int> jobs;
   double pieces = 0;
   {
-    auto owner = [](int64_t u, int64_t UU, int GG) { return (int64_t)(((u + 1) * GG - 1) / UU); };
     for (int i = 0; i < n; ++i) {
       const ProbeDesc& p = ga.d[i];
       for (int side = 0; side < 2; ++side) {
@@ -2025,10 +2061,13 @@ static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
         const int ph = sd2.ph + 1;  // phase B = 1, C = 2
         for (int ct = 0; ct < nct; ++ct) {
           const int64_t u0 = sd2.pre + (int64_t)ct * sd2.S;
-          const int64_t np = owner(u0 + sd2.S - 1, U[ph], G[ph]) - owner(u0, U[ph], G[ph]) + 1;
+          const int np = plan_owner(bounds[ph], u0 + sd2.S - 1) - plan_owner(bounds[ph], u0) + 1;
           if (np > 1) {
+            HDP_CHECK_ARG(np <= sd2.kmax, "probe sweep: a stripe has more pieces than its buffer holds");
             jobs.push_back(i);
             jobs.push_back(2 * ct + side);
+            jobs.push_back(np);
+            jobs.push_back(0);
             // the finish reads the pieces and updates the gradient of split stripes only
             pieces += 4.0 * p.r * kSwC * ((double)np + (p.accumulate ? 2 : 1));
           }
@@ -2036,7 +2075,7 @@ static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
       }
     }
   }
-  const int njobs = (int)(jobs.size() / 2);
+  const int njobs = (int)(jobs.size() / 4);
   HDP_CHECK_ARG((int64_t)njobs * (rp * kSwC / 256) < (1ll << 31), "probe sweep: finish grid too large");
   const size_t o_j = place(sizeof(int) * jobs.size());
   size_t tab_cap = kTableFixed + (size_t)n * table_per_module();
@@ -2045,7 +2084,8 @@ static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
   std::vector<char> blob(off);
   for (int ph = 0; ph < 3; ++ph) {
     memcpy(blob.data() + o_sd[ph], sd[ph].data(), sizeof(SweepDesc) * sd[ph].size());
-    phase_starts(sd[ph], U[ph], G[ph], reinterpret_cast<int*>(blob.data() + o_w[ph]));
+    phase_starts(sd[ph], bounds[ph], G[ph], reinterpret_cast<int*>(blob.data() + o_w[ph]),
+                 reinterpret_cast<int*>(blob.data() + o_b[ph]));
   }
   for (int k = 0; k < 2; ++k) memcpy(blob.data() + o_y[k], yd[k].data(), sizeof(YRedDesc) * n);
   memcpy(blob.data() + o_f, fd.data(), sizeof(FinDesc) * n);
@@ -2060,7 +2100,7 @@ static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
   SweepArgs sa[3];
   for (int ph = 0; ph < 3; ++ph)
     sa[ph] = SweepArgs{(int)sd[ph].size(), G[ph], spin, U[ph], err, errd, reinterpret_cast<const SweepDesc*>(tab + o_sd[ph]),
-                       reinterpret_cast<const int*>(tab + o_w[ph])};
+                       reinterpret_cast<const int*>(tab + o_w[ph]), reinterpret_cast<const int*>(tab + o_b[ph])};
   // workspace bytes the reduce / finish passes move (slabs + Y; pieces + gradients) -- counted
   // as algorithmic for these launches: they are the price of the stripe decomposition
   double slab[2] = {0, 0};
@@ -2122,7 +2162,7 @@ static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
   HDP_CHECK_LAUNCH();
   if (njobs) {  // (none when every stripe had one segment: no launch)
     const int bx = (rp * kSwC + 256 * V - 1) / (256 * V);
-    SwFinishArgs fa{n, rp, {U[1], U[2]}, {G[1], G[2]}, reinterpret_cast<const FinDesc*>(tab + o_f),
+    SwFinishArgs fa{n, rp, reinterpret_cast<const FinDesc*>(tab + o_f),
                     reinterpret_cast<const int*>(tab + o_j), bx};
     KTimer kt(K_PROBE_FINISH, st, pieces);
     if (v4)
