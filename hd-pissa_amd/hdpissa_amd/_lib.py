@@ -82,6 +82,11 @@ SIGNATURES = {
     "hdp_probe_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_int]),
     "hdp_probe_grads": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int,
                                  _c_vp, _c_vp, _c_f, _c_int, _c_vp, _c_sz, _c_vp]),
+    "hdp_probe_dropout_workspace_bytes": (_c_sz, [_c_i64, _c_i64, _c_i64, _c_int]),
+    "hdp_probe_grads_dropout": (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_int,
+                                         _c_vp, _c_vp, _c_f, _c_int, _c_f, ctypes.c_uint64, ctypes.c_uint64, _c_vp,
+                                         _c_sz, _c_vp]),
+    "hdp_dropout_mask": (_c_int, [_c_i64, _c_i64, _c_f, ctypes.c_uint64, ctypes.c_uint64, _c_vp, _c_vp]),
     "hdp_probe_group_max": (_c_int, []),
     "hdp_probe_errors": (_c_int, [_c_int]),
     "hdp_probe_host_wait_us": (_c_i64, [_c_int]),

@@ -21,7 +21,10 @@ What changes underneath (MI355X-native):
     hp:139 is below float32 resolution of the output and is not formed;
   * backward: the probe gradients come from skinny fp32-MFMA kernels (K2) written straight
     into a flat factor arena that the step's single Adam launch (K3) and the all-gather
-    consume; A.grad / B.grad are views of that arena with the reference's 1e-16 scale.
+    consume; A.grad / B.grad are views of that arena with the reference's 1e-16 scale;
+  * dropout > 0 (train mode): the backward of a call runs the fused masked kernel at once with
+    that call's (seed, offset) -- ``layer.dropout_calls`` / ``layer.last_dropout_state``, mask
+    contract in ``hdpissa_amd.dropout``; the forward output and dX are untouched.
 """
 from __future__ import annotations
 
@@ -310,6 +313,16 @@ class _ProbeLinearFn(torch.autograd.Function):
     def forward(ctx, x, W_res, bias, A, B, layer):
         ctx.save_for_backward(x)
         ctx.layer = layer
+        p = layer.dropout_rate
+        if layer.training and p and 0 < p:
+            # the mask applies: draw this call's (seed, offset) -- see hdpissa_amd.dropout for the contract
+            seed = torch.cuda.initial_seed()
+            offset = (layer._arena_index << 32) | (layer.dropout_calls & 0xFFFFFFFF)
+            layer.dropout_calls += 1
+            layer.last_dropout_state = (seed, offset)
+            ctx.dropout = (float(p), seed, offset)
+        else:
+            ctx.dropout = None
         return F.linear(x, W_res, bias)
 
     @staticmethod
@@ -317,7 +330,7 @@ class _ProbeLinearFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         layer = ctx.layer
         dx = gy.matmul(layer.W_res) if ctx.needs_input_grad[0] else None
-        layer._probe_backward(x, gy)
+        layer._probe_backward(x, gy, ctx.dropout)
         return dx, None, None, None, None, None
 
 
@@ -336,13 +349,17 @@ class CustomLinearLayer(nn.Module):
         self.dropout_rate = dropout
         self.dropout = nn.Dropout(p=dropout)
         self.alpha = _alpha_eff(alpha, ranks_per_gpu)                        # hp:103
-        if dropout and dropout > 0:
+        self._ops = ops
+        if dropout and dropout > 0 and not hasattr(self.ops, "probe_grads_dropout"):
             raise NotImplementedError(
-                "dropout > 0 acts elementwise on the dense out x in product B@A (hp:139), which the "
-                "skinny MI355X probe path never forms; the reference configurations use dropout=0.0")
+                "dropout > 0 acts elementwise on the dense out x in product B@A (hp:139); it needs the fused "
+                "masked probe backward (probe_grads_dropout), which this op set does not have")
+        # masked forwards so far: the low half of the next call's RNG offset (a resumed run restarts it
+        # unless the caller restores it); last_dropout_state = the (seed, offset) of the last masked forward
+        self.dropout_calls = 0
+        self.last_dropout_state: Optional[Tuple[int, int]] = None
         self.r = int(ranks_per_gpu)
         self.device_id, self.world_size = device_id, world_size
-        self._ops = ops
         W = original_linear.weight.data
         if _factors is None:
             _factors = self.ops.svd_topk(W, self.r, world_size)[:2]        # hp:106-125
@@ -372,6 +389,7 @@ class CustomLinearLayer(nn.Module):
     def _bind(self, arena: FactorArena, oa: int, ob: int) -> None:
         r, inn, out = self.r, self.in_features, self.out_features
         self._arena = arena
+        self._arena_index = arena.layers.index(self)  # the high half of a masked call's RNG offset
         self._oa, self._ob = oa, ob
         self.A = nn.Parameter(arena.fac[oa:oa + r * inn].view(r, inn))
         self.B = nn.Parameter(arena.fac[ob:ob + out * r].view(out, r))
@@ -406,11 +424,14 @@ class CustomLinearLayer(nn.Module):
         """alpha_eff * 1e-16 in float32 (hp:139's `*1e-16*self.alpha`)."""
         return float(np.float32(self.alpha) * np.float32(1e-16))
 
-    def _probe_backward(self, x: torch.Tensor, gy: torch.Tensor) -> None:
+    def _probe_backward(self, x: torch.Tensor, gy: torch.Tensor,
+                        dropout: Optional[Tuple[float, int, int]] = None) -> None:
         """Called from autograd (or directly): schedule A.grad += s (G B)^T X and
-        B.grad += s G^T (X A^T) on the arena's probe queue (grouped K2 launch)."""
+        B.grad += s G^T (X A^T) on the arena's probe queue (grouped K2 launch).  ``dropout`` =
+        (p, seed, offset) of a masked forward: the fused masked kernel runs at once on the current
+        stream instead (A.grad += s/(1-p) B^T (M . G^T X), B.grad += s/(1-p) (M . G^T X) A^T)."""
         fs = self._fslot
-        if fs is not None and fs.push(self._parameters, x, gy):
+        if dropout is None and fs is not None and fs.push(self._parameters, x, gy):
             return  # the native push did every check below (hdp_torch_ext.cpp LayerSlot)
         q = self._arena.probe_queue
         A, B = self.A, self.B
@@ -441,6 +462,9 @@ class CustomLinearLayer(nn.Module):
                 gA.zero_()
                 gB.zero_()
             return
+        if dropout is not None:
+            self._masked_backward(x, gy, gA, gB, scale, accumulate, dropout)
+            return
         if q.native_ok(self, x, gA, gB):
             # the native push takes [..., in] / [..., out] activations as they come (contiguity,
             # dtype of G and 16-byte alignment are handled there)
@@ -458,6 +482,29 @@ class CustomLinearLayer(nn.Module):
         if G.data_ptr() & 15:
             G = G.clone()
         q.enqueue(self, X, G, gA, gB, scale, accumulate)
+
+    def _masked_backward(self, x, gy, gA, gB, scale, accumulate, dropout) -> None:
+        """The masked probe backward of one call (never queued: every call has its own mask)."""
+        p, seed, offset = dropout
+        q = self._arena.probe_queue
+        if q.pending(self):  # queued unmasked calls of this layer write the same gradients: keep the order
+            q.flush()
+        if p >= 1.0:  # everything dropped: the call contributes exactly zero
+            if not accumulate:
+                gA.zero_()
+                gB.zero_()
+            return
+        inn, out = self.in_features, self.out_features
+        X = x if (x.dim() == 2 and x.is_contiguous()) else x.reshape(-1, inn).contiguous()
+        G = gy if (gy.dim() == 2 and gy.is_contiguous()) else gy.reshape(-1, out).contiguous()
+        if G.dtype != X.dtype:
+            G = G.to(X.dtype)
+        if X.data_ptr() & 15:
+            X = X.clone()
+        if G.data_ptr() & 15:
+            G = G.clone()
+        self.ops.probe_grads_dropout(X, G, self.A.detach(), self.B.detach(), gA, gB, scale, accumulate, p, seed,
+                                     offset, Bt=self._b_transposed())
 
     def _fill_probe_item(self, carr, n, X, G, gA, gB, accumulate) -> int:
         """Fill slot n of the queue's ctypes ProbeItem array; returns its workspace bytes."""

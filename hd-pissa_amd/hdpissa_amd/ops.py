@@ -16,6 +16,9 @@ from . import _lib
 from ._lib import HDP_BF16, HDP_F32, check, lib
 
 
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -172,6 +175,47 @@ class HipOps:
         check(lib().hdp_probe_grads(T, inn, out, r, X.data_ptr(), G.data_ptr(), _dt(X), A.data_ptr(), Bp.data_ptr(),
                                     btr, gA.data_ptr(), gB.data_ptr(), float(scale), int(bool(accumulate)),
                                     ws.data_ptr(), ws.numel(), _stream()), "hdp_probe_grads")
+
+    def probe_grads_dropout(self, X: torch.Tensor, G: torch.Tensor, A: torch.Tensor, B: torch.Tensor,
+                            gA: torch.Tensor, gB: torch.Tensor, scale: float, accumulate: bool, p: float,
+                            seed: int, offset: int, Bt: Optional[torch.Tensor] = None) -> None:
+        """probe_grads with the reference's dropout on the dense product (hp:139): with the keep mask M of
+        (p, seed, offset) (hdpissa_amd.dropout) and D = G^T X,  gA (+)= scale/(1-p) B^T (M . D);
+        gB (+)= scale/(1-p) (M . D) A^T.  0 < p < 1; bitwise reproducible."""
+        _need_gpu(X, G, A, B, gA, gB)
+        _f32(A, B, gA, gB)
+        if X.dtype != G.dtype:
+            raise TypeError("X and G must share the model dtype")
+        T, inn = X.shape
+        out = G.shape[1]
+        r = A.shape[0]
+        if G.shape[0] != T or A.shape[1] != inn or B.shape != (out, r) or gA.shape != A.shape or gB.shape != B.shape:
+            raise ValueError("probe_grads_dropout: shape mismatch")
+        for t in (X, G, A, B, gA, gB):
+            if not t.is_contiguous():
+                raise ValueError("probe_grads_dropout: tensors must be contiguous")
+        if Bt is not None:
+            _need_gpu(Bt)
+            _f32(Bt)
+            if Bt.shape != (r, out) or not Bt.is_contiguous():
+                raise ValueError("probe_grads_dropout: Bt must be a contiguous r x out tensor")
+        nb = lib().hdp_probe_dropout_workspace_bytes(T, inn, out, r) if T > 0 else 0
+        ws = self._workspace("probe_dropout", nb, X.device)
+        Bp, btr = (Bt, 1) if Bt is not None else (B, 0)
+        check(lib().hdp_probe_grads_dropout(T, inn, out, r, X.data_ptr(), G.data_ptr(), _dt(X), A.data_ptr(),
+                                            Bp.data_ptr(), btr, gA.data_ptr(), gB.data_ptr(), float(scale),
+                                            int(bool(accumulate)), float(p), int(seed) & _U64, int(offset) & _U64,
+                                            ws.data_ptr(), ws.numel(), _stream()), "hdp_probe_grads_dropout")
+
+    def dropout_mask(self, out: int, inn: int, p: float, seed: int, offset: int, device=None) -> torch.Tensor:
+        """The keep mask (uint8, out x in, 1 = kept) of a masked call, from the kernel's own mask function."""
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        mask = torch.empty(int(out), int(inn), dtype=torch.uint8, device=dev)
+        _need_gpu(mask)
+        with torch.cuda.device(dev):
+            check(lib().hdp_dropout_mask(int(out), int(inn), float(p), int(seed) & _U64, int(offset) & _U64,
+                                         mask.data_ptr(), _stream()), "hdp_dropout_mask")
+        return mask
 
     def probe_errors(self, clear: bool = False) -> int:
         """The probe's device error word (a sweep hand-off wait gave up in a completed launch):

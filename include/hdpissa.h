@@ -215,6 +215,29 @@ int hdp_probe_grads(int64_t T, int64_t in, int64_t out, int r, const void* X, co
                     float* gB, float scale, int accumulate, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* K2 with adapter dropout -- hp:139 with dropout > 0: the reference drops elements of the dense
+ * out x in product B A and scales the kept ones by 1 / (1 - p).  With the keep mask M (below) and
+ * D = G^T X (out x in, float32 accumulation over the T tokens):
+ *   gA (r x in)  += scale / (1 - p) * B^T (M . D)
+ *   gB (out x r) += scale / (1 - p) * (M . D) A^T
+ * D is formed tile by tile on MFMA (float32 activations: the exact f32 chain; bf16 activations: bf16
+ * MFMA, whose products are exact in float32), masked in registers and contracted against B and A at
+ * once; nothing out x in reaches memory.  Partial sums go to the workspace and are folded in a fixed
+ * order: the same inputs, seed and offset give bitwise equal gradients.  Operands, alignment and
+ * r <= 128 as hdp_probe_grads; 0 < p < 1.  T == 0 writes zeros (accumulate == 0) or nothing.
+ * Mask: element e = o * in + i is decided by Philox4x32-10 with key (lo32 seed, hi32 seed) and
+ * counter (lo32(e >> 2), hi32(e >> 2), lo32 offset, hi32 offset): it is DROPPED iff output word
+ * [e & 3] < min(2^32 - 1, floor((double)p * 2^32)).  hdp_dropout_mask writes that mask (1 = kept)
+ * with the same device function the fused kernel calls. */
+size_t hdp_probe_dropout_workspace_bytes(int64_t T, int64_t in, int64_t out, int r);
+int hdp_probe_grads_dropout(int64_t T, int64_t in, int64_t out, int r, const void* X, const void* G,
+                            int x_dtype, const float* A, const float* B, int b_transposed,
+                            float* gA, float* gB, float scale, int accumulate,
+                            float p, uint64_t seed, uint64_t offset,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int hdp_dropout_mask(int64_t out, int64_t in, float p, uint64_t seed, uint64_t offset,
+                     uint8_t* mask /* out x in, 1 = kept */, void* stream);
+
 /* Grouped form: up to hdp_probe_group_max() modules (same ceil(r/16) block, same x_dtype, no
  * two items sharing a gradient) in one launch per pass -- what an autograd backward over a
  * decoder layer produces.  items is a HOST array read during the call; the workspace must
