@@ -53,15 +53,24 @@ HDP_HD unsigned dropout_keep4(uint64_t e0, const DropoutKey& k) {
   const unsigned sh = static_cast<unsigned>(e0 & 3);
   const Philox4 a = philox4x32_10(static_cast<uint32_t>(blk), static_cast<uint32_t>(blk >> 32), k.off_lo, k.off_hi,
                                   k.seed_lo, k.seed_hi);
+  // (the keep bit is a statement of its own: with `bits |= (a.w[j] >= ... ? 1u : 0u) << j` in one expression,
+  // g++ 11 -fsanitize=undefined indexes w with an uninitialized copy of j -- tests/test_dropout_host.py builds
+  // this header that way; the device code is the same either way)
   unsigned bits = 0;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) bits |= (a.w[j] >= k.thresh ? 1u : 0u) << j;
+  for (int j = 0; j < 4; ++j) {
+    const unsigned kept = a.w[j] >= k.thresh ? 1u : 0u;
+    bits |= kept << j;
+  }
   if (sh == 0) return bits;
   const uint64_t nb = blk + 1;
   const Philox4 b = philox4x32_10(static_cast<uint32_t>(nb), static_cast<uint32_t>(nb >> 32), k.off_lo, k.off_hi,
                                   k.seed_lo, k.seed_hi);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) bits |= (b.w[j] >= k.thresh ? 1u : 0u) << (4 + j);
+  for (int j = 0; j < 4; ++j) {
+    const unsigned kept = b.w[j] >= k.thresh ? 1u : 0u;
+    bits |= kept << (4 + j);
+  }
   return (bits >> sh) & 15u;
 }
 

@@ -1,8 +1,13 @@
 """Adapter dropout on the host (CPU): the numpy replica of the RNG contract against the Random123 known
 answers, the statistics of its mask, the C-ABI's argument checks (no GPU touched) and the op-set gate of the
-layer constructor."""
+layer constructor; and the header the kernels share (csrc/hdp_philox.h), compiled with the host compiler --
+plain and with -fsanitize=address,undefined -- behind tests/philox_check.cpp: its Philox, its threshold and
+dropout_keep4 at every residue of e0 (the fused kernel's indexing when `in` is no multiple of 4) against the
+replica, from 0 and around element 2^34."""
 import math
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -76,6 +81,116 @@ def test_mask_reference_element_rule():
         e = o * inn + i
         w = philox4x32_10((e >> 2, 0, 4, 2), (9, 7))[e & 3]
         assert int(m[o, i]) == int(int(np.asarray(w).reshape(-1)[0]) >= th)
+
+
+# ---- the kernels' own header (csrc/hdp_philox.h) on the host: tests/philox_check.cpp prints what it computes ----
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PHILOX_SRC = os.path.join(ROOT, "tests", "philox_check.cpp")
+PHILOX_INC = os.path.join(ROOT, "hd-pissa_amd", "csrc")
+H_SEED = (0x1234 << 32) | 0x9E3779B9   # above 2^32
+H_OFF = (5 << 32) | 0xFFFFFFFE         # above 2^32
+KEEP_PS = [0.3, 0.5, 1e-9, 0.999]
+HI = 1 << 34  # element index whose block index is 2^32: the counter's low word wraps, the high word becomes 1
+
+
+def _cxx():
+    for c in (os.environ.get("CXX"), "g++", "c++", "clang++"):
+        if c and shutil.which(c):
+            return c
+    return None
+
+
+def _pbits(p):
+    return hex(int(np.float32(p).view(np.uint32)))
+
+
+@pytest.fixture(scope="module", params=[("-O2",), ("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")],
+                ids=["plain", "asan-ubsan"])
+def philox_exe(request, tmp_path_factory):
+    cxx = _cxx()
+    assert cxx is not None, "no host C++ compiler"
+    exe = str(tmp_path_factory.mktemp("philox") / "philox_check")
+    # g++ does not know the header's `#pragma unroll`
+    subprocess.run([cxx, "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", *request.param, "-I", PHILOX_INC,
+                    PHILOX_SRC, "-o", exe], check=True)
+
+    def run(*args):
+        p = subprocess.run([exe, *[str(a) for a in args]], capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        return p.stdout.split()
+    return run
+
+
+def _nibbles(keep):
+    """keep[j] = 1 if element e_start + j is kept -> dropout_keep4 of e_start + j, j = 0 .. len - 4."""
+    k = np.asarray(keep, dtype=np.int64)
+    return k[:-3] | (k[1:-2] << 1) | (k[2:-1] << 2) | (k[3:] << 3)
+
+
+def _keep_by_hand(e, p, seed, offset):
+    """The contract with the counter written out: no use of dropout_mask_reference."""
+    from hdpissa_amd.dropout import dropout_threshold, philox4x32_10
+    e = np.asarray(e, dtype=np.uint64)
+    blk = e >> np.uint64(2)
+    words = philox4x32_10((blk & np.uint64(0xFFFFFFFF), blk >> np.uint64(32), offset & 0xFFFFFFFF, offset >> 32),
+                          (seed & 0xFFFFFFFF, seed >> 32))
+    word = np.choose((e & np.uint64(3)).astype(np.int64), [np.broadcast_to(w, e.shape) for w in words])
+    return (word >= np.uint32(dropout_threshold(p))).astype(np.int64)
+
+
+def test_header_philox_known_answers(philox_exe):
+    for counter, key, want in KAT:
+        got = philox_exe("philox", *counter, *key)
+        assert tuple(int(w, 16) for w in got) == want
+
+
+def test_header_threshold(philox_exe):
+    from hdpissa_amd.dropout import dropout_threshold
+    ps = [0.1, 0.3, 0.5, 0.999, 1e-9, 2.0 ** -33, 1.0 - 2.0 ** -24]
+    got = [int(t) for t in philox_exe("thresh", *[_pbits(p) for p in ps])]
+    assert got == [dropout_threshold(p) for p in ps]
+    assert got[2] == 1 << 31 and got[5] == 0 and got[4] == 4          # 2^-33: nothing is ever dropped
+    assert got[6] == (1 << 32) - 256                                    # 1 - 2^-24 is a float32: exact
+
+
+@pytest.mark.parametrize("p", KEEP_PS)
+def test_header_keep4_from_zero(philox_exe, p):
+    """dropout_keep4(e0) at 4096 consecutive e0, all four residues: the second block and the shift."""
+    from hdpissa_amd.dropout import dropout_mask_reference
+    n = 4096
+    keep = dropout_mask_reference(1, n + 3, p, H_SEED, H_OFF).reshape(-1)
+    want = _nibbles(keep)
+    assert np.array_equal(keep, _keep_by_hand(np.arange(n + 3), p, H_SEED, H_OFF))
+    (got,) = philox_exe("keep4", H_SEED, H_OFF, _pbits(p), 0, n)
+    assert len(got) == n
+    bad = [e for e in range(n) if int(got[e], 16) != want[e]]
+    assert not bad, f"p = {p}: dropout_keep4 differs from the replica at e0 = {bad[:8]} ({len(bad)} of {n})"
+
+
+@pytest.mark.parametrize("p", KEEP_PS)
+def test_header_keep4_around_2_to_34(philox_exe, p):
+    """Block indices 2^32 - 512 .. 2^32 + 512: the low counter word wraps and the high word is non-zero; at
+    e0 = 2^34 - 3 .. 2^34 - 1 the two blocks of one nibble differ in the high word."""
+    start, n = HI - 2048, 4096
+    want = _nibbles(_keep_by_hand(start + np.arange(n + 3), p, H_SEED, H_OFF))
+    (got,) = philox_exe("keep4", H_SEED, H_OFF, _pbits(p), start, n)
+    assert len(got) == n
+    bad = [start + j for j in range(n) if int(got[j], 16) != want[j]]
+    assert not bad, f"p = {p}: dropout_keep4 differs from the replica at e0 = {bad[:8]} ({len(bad)} of {n})"
+
+
+def test_header_keep4_expectation_sees_the_residue():
+    """The expected nibbles would catch a keep4 that ignored e0 & 3, or the counter's high word."""
+    for start in (0, HI - 2048):
+        e = start + np.arange(4096 + 3)
+        want = _nibbles(_keep_by_hand(e, 0.5, H_SEED, H_OFF))
+        j = np.arange(4096)
+        assert np.any(want[j] != want[j & ~3])
+    lo = _nibbles(_keep_by_hand(np.arange(4096 + 3), 0.5, H_SEED, H_OFF))
+    hi = _nibbles(_keep_by_hand(HI + np.arange(4096 + 3), 0.5, H_SEED, H_OFF))
+    assert np.any(lo != hi)
+    assert not np.array_equal(lo, _nibbles(_keep_by_hand(np.arange(4096 + 3), 0.5, H_SEED, H_OFF & 0xFFFFFFFF)))
+    assert not np.array_equal(lo, _nibbles(_keep_by_hand(np.arange(4096 + 3), 0.5, H_SEED & 0xFFFFFFFF, H_OFF)))
 
 
 def _lib_or_skip():

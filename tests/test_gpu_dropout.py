@@ -31,13 +31,25 @@ def _ops():
     return default_ops()
 
 
-@pytest.mark.parametrize("out,inn", [(392, 520), (264, 136)])
+# the last four: out * in no multiple of 4 (the last thread writes 1 - 3 elements); 3 x 1025 ends one element
+# into a second block of 256 threads
+@pytest.mark.parametrize("out,inn", [(392, 520), (264, 136), (1, 1), (7, 13), (75, 130), (3, 1025)])
 @pytest.mark.parametrize("p", [0.1, 0.5])
 def test_mask_equals_host_replica(out, inn, p):
+    from hdpissa_amd._lib import check, lib
     from hdpissa_amd.dropout import dropout_mask_reference
+    ref = dropout_mask_reference(out, inn, p, SEED, OFF0)
     m = _ops().dropout_mask(out, inn, p, SEED, OFF0)
     assert m.dtype == torch.uint8 and tuple(m.shape) == (out, inn)
-    assert np.array_equal(m.cpu().numpy(), dropout_mask_reference(out, inn, p, SEED, OFF0))
+    assert np.array_equal(m.cpu().numpy(), ref)
+    # the same call into a buffer with a guard behind the mask: nothing is written past out * in
+    n, guard = out * inn, 1024
+    buf = torch.full((n + guard,), 0xA5, dtype=torch.uint8, device=DEV)
+    check(lib().hdp_dropout_mask(out, inn, p, SEED, OFF0, buf.data_ptr(), torch.cuda.current_stream().cuda_stream),
+          "hdp_dropout_mask")
+    got = buf.cpu().numpy()
+    assert np.array_equal(got[:n], ref.reshape(-1))
+    assert np.all(got[n:] == 0xA5)
 
 
 @functools.lru_cache(maxsize=None)
