@@ -30,7 +30,6 @@
 #include <vector>
 
 #include "hdp_probe_int.h"
-#include "hdp_probe_plan.h"
 
 namespace hdp {
 
@@ -430,7 +429,7 @@ __global__ __launch_bounds__(256) void probe_finish4_kernel(GroupArgs ga) {
 // each gets >= kSwMinSteps steps); the U steps of the group, flattened as (module, stripe,
 // row step), are split into G equal contiguous ranges -- no tail quantization, one launch per
 // phase however large the group (plan_ranges, hdp_probe_plan.h; phase A of a float32 shared-X group cuts
-// ranges of equal COST instead, kSwWeightA).  A workgroup's range crosses few stripes; OUTER accumulators
+// ranges of equal COST instead, kSwWeightA; the whole host plan is hdp_sweep_plan.h).  A workgroup's range crosses few stripes; OUTER accumulators
 // live in registers over a stripe segment and are flushed as one piece per segment.
 //
 // Workgroup: 8 waves, each owning 64 columns of the stripe.  A lane loads 4 consecutive columns
@@ -442,7 +441,7 @@ __global__ __launch_bounds__(256) void probe_finish4_kernel(GroupArgs ga) {
 // unwritten pieces), so the loop is branch-free; loads run two steps ahead with three register
 // sets in fixed roles.
 // ---------------------------------------------------------------------------------------
-constexpr int kSwMinSteps = 8;       // >= 128 rows per workgroup: bounds the pieces per stripe
+// (kSwWaves, kSwC, kSwMinSteps, kSwMaxBlk and the descriptor structs: hdp_sweep_plan.h)
 // bf16 activations on bf16 MFMA (v_mfma_f32_16x16x16_bf16): X and G are exact in bf16, the f32 operand
 // (a factor fragment, or a row of the other stream's projection) is split exactly into three bf16
 // parts v = hi + mid + lo (24 significant bits), and the MFMA sums the three exact products in f32 --
@@ -528,40 +527,11 @@ constexpr int kSwRedBufs = 4;        // PROJ partial buffers in rotation (arriva
 // the shared-X instance (FUSE, 4 r-blocks of up to 4 modules): three (132 KB)
 template <int RB, bool FUSE = false>
 constexpr int sw_nbuf() { return FUSE ? 3 : RB >= 4 ? 2 : kSwRedBufs; }
-constexpr int kSwMaxBlk = 4;         // r-blocks of one stream side (FUSE: of all modules sharing its X)
 #ifndef HDP_BF_SETS
 #define HDP_BF_SETS 3
 #endif
 constexpr int kBfSets = HDP_BF_SETS;  // register sets of the bf16 PROJ phases (loads kBfSets - 1 steps ahead)
 enum { kSwProj = 1, kSwOuter = 2 };
-
-struct SweepDesc {
-  const void* Z;          // T x N, row-major, x_dtype
-  const float* F;         // f_rk: F[j][n] at j * N + n (A, B^T);  else F[n][j] at n * r + j (B)
-  float* slab_out;        // PROJ:  [nct][T][rp] stripe partials of Z F^T
-  const float* y_in;      // OUTER: the other stream's projection, row t at y_in + t * yrs, a lane's
-                          //        RB values at + li * yls (probe_yreduce_kernel's layout)
-  float* part;            // OUTER: [nct][kmax][rp][kSwC]  or  [nct][kmax][kSwC][rp] (part_t)
-  int64_t T, N, pre;      // pre: first flattened step of this module side
-  int r, f_rk, part_t, nct, S, kmax;  // S = 16-row steps per stripe
-  // OUTER, a stripe covered by ONE workgroup segment: its gradient block written directly,
-  // g (+)= scale * acc (part_t 0: gA [r][N]; 1: gB [N][ldb]); the finish pass skips it
-  float* g;
-  float scale;
-  int acc, ldb;
-  int yrs, yls;           // Y row / lane strides (floats)
-  // Shared-X instances (FUSE): the side is r-block-wise -- nb blocks of 16 rows, block b possibly of
-  // another module that reads the same X (q/k/v, gate/up).  Block b: F rows Fb[b] (rbr[b] of them),
-  // slab columns slab_b[b] and pieces part_b[b] (row strides rpm = the members' 16 RB), gradient
-  // rows gb[b] with scale sc[b] / accumulate accb[b].
-  int nb, rpm;
-  const float* Fb[kSwMaxBlk];
-  float* slab_b[kSwMaxBlk];
-  float* part_b[kSwMaxBlk];
-  float* gb[kSwMaxBlk];
-  float sc[kSwMaxBlk];
-  int rbr[kSwMaxBlk], accb[kSwMaxBlk];
-};
 
 // g (+)= s * acc for this wave's columns of one stripe (the finish kernel's arithmetic on a single
 // piece: s * (piece + 0) == s * piece, then g + v as two roundings)
@@ -1330,12 +1300,7 @@ __global__ __launch_bounds__(512, OCC == 2 ? 4 : 2) void probe_sweep_kernel(Swee
 
 // Y[t][j] = sum_ct slab[ct][t][j] (fixed order), all modules of a group in one launch:
 // blockIdx.y = module, blockIdx.x = 256-granule chunk of its T x rp / 4 f32x4 granules.
-struct YRedDesc {
-  const float* slab;  // [nct][T][rp] (rp = 16 RB of the module)
-  float* y;           // element (t, j = 16 b + li) -> y[t * ys + b + li * sl]
-  int64_t T;
-  int nct, ys, sl, pad;
-};
+// (YRedDesc: hdp_sweep_plan.h)
 struct YReduceArgs {
   int n, rp;
   const YRedDesc* d;  // [n] (device)
@@ -1367,21 +1332,7 @@ __global__ __launch_bounds__(256) void probe_yreduce_kernel(YReduceArgs ya) {
 }
 
 // gA[j][n] (+)= s * sum_k pieceA[ct][k][j][n % kSwC];  gB[n][j] (+)= s * sum_k pieceB[ct][k][n % kSwC][j]
-struct SwFinishSide {
-  const float* part;
-  int64_t pre;     // the OUTER phase's flattened steps before this side
-  int S, kmax;
-  int ph;          // which OUTER phase wrote the pieces: 0 = phase B, 1 = phase C
-  int pad;
-};
-struct FinDesc {
-  float* gA;
-  float* gB;
-  int in, out, r, acc;
-  float scale;
-  int ldb;  // row stride of gB (= r, or the full rank when the module is an r-slice of a wider one)
-  SwFinishSide sx, sg;
-};
+// (SwFinishSide, FinDesc: hdp_sweep_plan.h)
 struct SwFinishArgs {
   int n, rp;
   const FinDesc* d;  // [n] (device)
@@ -1434,11 +1385,9 @@ __global__ __launch_bounds__(256) void probe_sweep_finish_kernel(SwFinishArgs fa
 }
 
 // Per-flush descriptor tables: one host blob copied to the head of the group's device workspace
-// in stream order.  The host side goes through a ring of pinned staging buffers, each reused only
-// after the copy that last read it has executed (its event).
-// WG start tables (4 ints) and range boundaries (1 int, + the end) per phase, up to 4096 WGs/phase
-constexpr size_t kTableFixed = 3 * 4096 * 5 * sizeof(int) + 8192;
-constexpr size_t kTablePerModule = 3 * sizeof(SweepDesc) + 2 * sizeof(YRedDesc) + sizeof(FinDesc) + 64;
+// in stream order (its layout and size: plan_sweep_tables / sweep_table_bytes, hdp_sweep_plan.h).  The
+// host side goes through a ring of pinned staging buffers, each reused only after the copy that last
+// read it has executed (its event): probe_tables_upload below.
 
 // Device error word of the sweep's PROJ hand-off: pinned host memory mapped into the device, so the
 // host reads it without synchronising (it reflects every launch that has completed).  Written only
@@ -1537,18 +1486,8 @@ int probe_tables_upload(const std::vector<char>& blob, void* dst, hipStream_t st
 }
 
 // ---------------------------------------------------------------------------------------
-// host planning
+// host planning (the sweep path's: hdp_sweep_plan.h -- rb_of, ModPlan, plan_sweep_module, the launch plan)
 // ---------------------------------------------------------------------------------------
-static int rb_of(int r) {
-  const int rb = (r + 15) / 16;
-  return rb <= 1 ? 1 : rb <= 2 ? 2 : rb <= 4 ? 4 : 8;
-}
-
-struct ModPlan {
-  int ksh, ksj, kst, colh, colj;
-  size_t off_slabH, off_slabJ, off_partA, off_partB, off_yH, off_yJ, area, bytes;
-};
-
 static void p1_split(int64_t K, int& ks, int& cols) {
   const int64_t span = (int64_t)kP1Waves * p1_cols();
   ks = (int)((K + span - 1) / span);
@@ -1562,8 +1501,6 @@ static bool use_sweep(int RB) {
   const char* e = getenv("HDP_PROBE_PATH");
   return RB <= 4 && !(e && e[0] == 's' && e[1] == 'p');
 }
-// group-level tables per module (sweep descriptors)
-static size_t table_per_module() { return kTablePerModule; }
 
 // 64 < r <= 128 (r-block 8): the probe is separable in r -- A.grad rows j and B.grad columns j only
 // involve A's row j and B's column j -- so such a module runs as r-slices of at most 64 on the
@@ -1576,46 +1513,23 @@ static bool slice_r(int r, int b_transposed) {
 }
 static int n_slices(int r) { return (r + 63) / 64; }
 
-// the finish's job list (one int4 per split stripe) is part of the group's tables: room for every stripe
-static size_t finish_jobs_bytes(int64_t in, int64_t out) {
-  return (size_t)(((in + kSwC - 1) / kSwC + (out + kSwC - 1) / kSwC) * 16 + 255) / 256 * 256;
-}
-
-static int sweep_kmax(int64_t T) { return (int)(((T + 15) / 16 + kSwMinSteps - 1) / kSwMinSteps) + 2; }
-
 static ModPlan plan_module(int64_t T, int64_t in, int64_t out, int r) {
-  ModPlan p;
   const int RB = rb_of(r), rp = 16 * RB;
+  if (use_sweep(RB)) return plan_sweep_module(T, in, out, r);
+  ModPlan p;
   size_t off = 0;
   auto take = [&](size_t n) { size_t o = off; off += (n * 4 + 255) / 256 * 256; return o; };
-  if (use_sweep(RB)) {
-    p.ksh = (int)((in + kSwC - 1) / kSwC);
-    p.ksj = (int)((out + kSwC - 1) / kSwC);
-    p.colh = p.colj = 0;
-    p.kst = sweep_kmax(T);  // pieces per stripe (capacity)
-    // slabs [nct][T16][rp] and projections [T16][rp] floats (T16 = T rounded up to 16 rows)
-    const size_t T16 = (size_t)((T + 15) / 16) * 16;
-    p.off_slabH = take((size_t)p.ksh * T16 * rp);
-    p.off_slabJ = take((size_t)p.ksj * T16 * rp);
-    p.off_partA = take((size_t)p.ksh * p.kst * rp * kSwC);
-    p.off_partB = take((size_t)p.ksj * p.kst * rp * kSwC);
-    // projections: [T16][rp], or the padded shared-X layout [T16][16 lanes][4 blocks] (r-block <= 2)
-    const size_t yrow = RB <= 2 ? 64 : 2 * (size_t)rp;
-    p.off_yH = take(T16 * yrow);
-    p.off_yJ = take(T16 * yrow);
-  } else {
-    p1_split(in, p.ksh, p.colh);
-    p1_split(out, p.ksj, p.colj);
-    p.kst = (int)((T + kTC - 1) / kTC);
-    p.off_slabH = take((size_t)p.ksh * T * rp);
-    p.off_slabJ = take((size_t)p.ksj * T * rp);
-    p.off_partA = take((size_t)p.kst * rp * in);
-    p.off_partB = take((size_t)p.kst * rp * out);
-    p.off_yH = p.off_yJ = 0;
-  }
+  p1_split(in, p.ksh, p.colh);
+  p1_split(out, p.ksj, p.colj);
+  p.kst = (int)((T + kTC - 1) / kTC);
+  p.off_slabH = take((size_t)p.ksh * T * rp);
+  p.off_slabJ = take((size_t)p.ksj * T * rp);
+  p.off_partA = take((size_t)p.kst * rp * in);
+  p.off_partB = take((size_t)p.kst * rp * out);
+  p.off_yH = p.off_yJ = 0;
   p.area = off;
   // + this module's share of the group's tables and counters
-  p.bytes = off + table_per_module() + kTableFixed + 256 + (use_sweep(RB) ? finish_jobs_bytes(in, out) : 0);
+  p.bytes = off + kTablePerModule + kTableFixed + 256;
   return p;
 }
 
@@ -1696,479 +1610,169 @@ static int launch_group(const GroupArgs& ga, hipStream_t st) {
   return HDP_OK;
 }
 
-// resident 512-thread workgroups of one sweep kernel instance x CUs (cached per instance/device)
-template <int DT, int RB, int MODE, bool VEC, int OCC, bool FUSE = false, bool K32 = false>
-static int sweep_slots(size_t lds) {
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  if (cached[dev] == 0) {
-    int cus = 0, per = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, probe_sweep_kernel<DT, RB, MODE, VEC, OCC, FUSE, K32>, 512,
-                                                     lds) != hipSuccess ||
-        per <= 0)
-      per = 1;
-    cached[dev] = cus * per;
-  }
-  return cached[dev];
-}
+// One kernel instance of a sweep phase and its dynamic LDS bytes.  The persistent schedule needs every
+// workgroup of a launch resident (PROJ hand-offs spin on arrival counters), so the instance whose occupancy
+// sizes the grid must be the instance launched: both take it from here.
+struct SweepKernel {
+  void (*fn)(SweepArgs);
+  size_t lds;
+};
 
-// resident workgroups of one phase: occupancy x CUs, capped so each gets >= kSwMinSteps steps
-template <int DT, int RB, int MODE, bool VEC, int OCC, bool FUSE = false, bool K32 = false>
-static int phase_grid(int64_t U, size_t lds) {
-  const int64_t cap = U / kSwMinSteps;
-  const int slots = sweep_slots<DT, RB, MODE, VEC, OCC, FUSE, K32>(lds);
-  return (int)(cap < 1 ? 1 : (cap < slots ? cap : slots));
-}
-
-// Cost of one 16-row step of a side with nb r-blocks, relative to nb = 1 (x 64), in phase A of a float32
-// shared-X group (the FUSE X6 PROJ instance).  A step's MFMA and LDS work grows with nb while its bytes do
-// not, so the q/k/v sets (3 blocks) and gate/up (2) take longer per step than o_proj / down_proj (1); an
-// equal split of the steps left the light workgroups idle at the phase's end (LLaMA-2-7B group: 420 -> 370 us).
-// Measured per step on homogeneous groups at the LLaMA-2-7B shapes (tools/probe_weights.py):
-// profiles/r07_probe_weights.jsonl -- 1 : 1.15 : 1.37 : 1.54.  Phase C (f32 OUTER) measured 1 : 0.94 : 1.13 :
-// 1.49: its 3-block steps are not the 1.3 x that would explain its time, so it keeps the equal split.
-constexpr int kSwWeightA[kSwMaxBlk + 1] = {64, 64, 74, 88, 98};
-// env HDP_PROBE_BALANCE=0: the equal split w * U / G in every phase (A/B measurements, tests)
-static bool probe_balance() {
-  const char* e = getenv("HDP_PROBE_BALANCE");
-  return !(e && e[0] == '0');
-}
-
-// the ranges of one phase's workgroups (plan_ranges); weights = per-nb step costs, or null for equal steps
-static int phase_ranges(const std::vector<SweepDesc>& d, int G, const int* weights, std::vector<int64_t>& bounds) {
-  std::vector<PlanSide> sides(d.size());
-  for (size_t i = 0; i < d.size(); ++i) {
-    const int nb = d[i].nb < 1 ? 1 : d[i].nb > kSwMaxBlk ? kSwMaxBlk : d[i].nb;
-    sides[i] = PlanSide{d[i].pre, d[i].nct, d[i].S, weights ? weights[nb] : 1};
-  }
-  return plan_ranges(sides, G, kSwMinSteps, bounds);
-}
-
-// where workgroup w of G starts: (module, stripe, step) of flattened step bounds[w], and the workgroups before
-// it on that stripe (its first segment's piece index); bnd = the device's bounds
-static void phase_starts(const std::vector<SweepDesc>& d, const std::vector<int64_t>& bounds, int G, int* out,
-                         int* bnd) {
-  int m = 0;
-  for (int w = 0; w <= G; ++w) bnd[w] = (int)bounds[w];
-  for (int w = 0; w < G; ++w) {
-    const int64_t lo = bounds[w];
-    while (m + 1 < (int)d.size() && lo >= d[m + 1].pre) ++m;
-    const int64_t rem = lo - d[m].pre;
-    out[4 * w] = m;
-    out[4 * w + 1] = (int)(rem / d[m].S);
-    out[4 * w + 2] = (int)(rem % d[m].S);
-    out[4 * w + 3] = w - plan_owner(bounds, lo - rem % d[m].S);
-  }
-}
-
-// Shared X (hp:139 is called with ONE hidden state per projection group of a decoder layer: q/k/v
-// read the same normed x, gate/up the same x; autograd saves that one tensor for each of them).
-// Modules of a group whose X is the same tensor (same pointer, T and in; B given transposed) are
-// packed into sets of at most kSwMaxBlk r-blocks; a set streams its X ONCE per pass for all of its
-// modules (phase A: PROJ against the stacked A rows; phase C: OUTER against the stacked
-// projections of their G) instead of once per module.  A set is formed only when X is the smaller
-// side (in <= sum of its modules' out): X is then the stream read twice.  env HDP_PROBE_SHARE_X=0
-// turns it off (A/B measurements, tests).
-// 0: off (HDP_PROBE_K32=0); 1: r-block 4 only (HDP_PROBE_K32=4); 2 (default): PROJ phases at every r-block,
-// the OUTER phase at r-block 4 (its r-block-1 instance spills 24 VGPRs); 3: every phase and r-block
-// (HDP_PROBE_K32=all)
-static int probe_k32() {
+// the switches of a launch (read per call: tests flip them per case)
+static SweepKnobs sweep_knobs() {
+  auto on = [](const char* name) {
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+  };
+  SweepKnobs kn;
+  kn.share_x = on("HDP_PROBE_SHARE_X");  // 0: no X-sharing sets (A/B measurements, tests)
+  kn.balance = on("HDP_PROBE_BALANCE");  // 0: the equal split w * U / G in every phase (A/B measurements, tests)
+  // 0: off (HDP_PROBE_K32=0); 1: r-block 4 only (HDP_PROBE_K32=4); 2 (default): PROJ phases at every r-block,
+  // the OUTER phase at r-block 4 (its r-block-1 instance spills 24 VGPRs); 3: every phase and r-block
+  // (HDP_PROBE_K32=all)
   const char* e = getenv("HDP_PROBE_K32");
-  return !e ? 2 : e[0] == '0' ? 0 : e[0] == '4' ? 1 : e[0] == 'a' ? 3 : 2;
-}
-// float32 activations: phase A (the shared-X FUSE instance, 4 r-block template) on the exact 6-product
-// bf16 split (X6, r04); env HDP_PROBE_X6=0 keeps f32 MFMA
-static bool probe_x6() {
-  const char* e = getenv("HDP_PROBE_X6");
-  return !(e && e[0] == '0');
-}
-static bool share_x_enabled() {
-  const char* e = getenv("HDP_PROBE_SHARE_X");
-  return !(e && e[0] == '0');
-}
-static std::vector<std::vector<int>> shared_x_sets(const HostGroup& ga) {
-  std::vector<std::vector<int>> sets;
-  const int n = ga.n;
-  if (ga.RB > 2 || !share_x_enabled()) return sets;
-  for (int i = 0; i < n; ++i)
-    if (!ga.d[i].b_t) return sets;
-  std::vector<char> used(n, 0);
-  for (int i = 0; i < n; ++i) {
-    if (used[i]) continue;
-    const ProbeDesc& p = ga.d[i];
-    std::vector<int> cur{i};
-    int64_t outs = p.out;
-    for (int k = i + 1; k < n && (int)(cur.size() + 1) * ga.RB <= kSwMaxBlk; ++k) {
-      const ProbeDesc& q = ga.d[k];
-      if (!used[k] && q.X == p.X && q.T == p.T && q.in == p.in) {
-        cur.push_back(k);
-        outs += q.out;
-      }
-    }
-    if (cur.size() < 2 || outs < p.in) continue;
-    for (int k : cur) used[k] = 1;
-    sets.push_back(cur);
-  }
-  return sets;
+  kn.k32 = !e ? 2 : e[0] == '0' ? 0 : e[0] == '4' ? 1 : e[0] == 'a' ? 3 : 2;
+  // float32 activations: phase A (the shared-X FUSE instance, 4 r-block template) on the exact 6-product
+  // bf16 split (X6, r04); env HDP_PROBE_X6=0 keeps f32 MFMA
+  kn.x6 = on("HDP_PROBE_X6");
+  return kn;
 }
 
-// the plain side descriptor of one module stream (X: PROJ -> H, OUTER with J -> pieces A; G: PROJ
-// -> J, OUTER with H -> pieces B^T), its r-block view filled for the FUSE instances
-static SweepDesc side_desc(const ProbeDesc& p, bool xs, int RB, int S) {
-  const int rp = 16 * RB;
-  SweepDesc d{};
-  d.Z = xs ? p.X : p.G;
-  d.F = xs ? p.A : p.B;
-  d.slab_out = xs ? p.slabH : p.slabJ;
-  d.y_in = xs ? p.yJ : p.yH;
-  d.part = xs ? p.partA : p.partB;
-  d.T = p.T;
-  d.N = xs ? p.in : p.out;
-  d.pre = 0;
-  d.r = p.r;
-  d.f_rk = xs ? 1 : p.b_t;
-  d.part_t = xs ? 0 : 1;
-  d.nct = xs ? p.ksh : p.ksj;
-  d.S = S;
-  d.kmax = p.kst;
-  d.g = xs ? p.gA : p.gB;
-  d.scale = p.scale;
-  d.acc = p.accumulate;
-  d.ldb = xs ? p.r : p.ldb;
-  d.yrs = rp;
-  d.yls = RB;
-  d.nb = RB;
-  d.rpm = rp;
-  for (int b = 0; b < kSwMaxBlk; ++b) {
-    const int rows = p.r - 16 * b;
-    d.rbr[b] = b < RB ? (rows < 0 ? 0 : rows > 16 ? 16 : rows) : 0;
-    d.Fb[b] = d.F + (int64_t)16 * b * d.N;  // f_rk rows (FUSE requires B^T)
-    d.slab_b[b] = d.slab_out + 16 * b;
-    d.part_b[b] = d.part_t ? d.part + 16 * b : d.part + (int64_t)16 * b * kSwC;
-    d.gb[b] = d.part_t ? d.g + 16 * b : d.g + (int64_t)16 * b * d.N;
-    d.sc[b] = p.scale;
-    d.accb[b] = p.accumulate;
-  }
-  return d;
-}
-
-// phases A (PROJ over S1), R1 (reduce S1 slabs), B (PROJ + OUTER over S2), R2 (reduce S2
-// slabs), C (OUTER over S1), D (finish); `tab` = the group's device table region
+// The instances of phases A, B and C for a group with (fuse) or without X-sharing sets.
 // occupancy per phase (measured r02, LLaMA-2-7B shapes): PROJ + OUTER (B) gains from two
 // resident workgroups per CU (-4 %), PROJ (A) and OUTER (C) from two steps of loads in flight
-// With X-sharing sets (shared_x_sets) phases A and C run the FUSE instance (4 r-blocks, runtime nb)
-// over every S1 side; phase B, the reduces and the finish keep their kernels (descriptor strides).
 template <int DT, int RB, bool VEC>
-static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
+static void pick_sweep(bool fuse, const SweepKnobs& kn, SweepKernel (&pk)[3]) {
   constexpr int rp = 16 * RB;
-  // bf16 data at r-block 4: phase B is PROJ only (bf16 MFMA, split fragments -- fused with OUTER they
-  // do not fit beside its accumulators) and S2's OUTER joins S1's in phase C: S2 is read twice, its
-  // projection costs a fifth of the f32 MFMA issue time
-  constexpr bool SPLIT_B = RB >= 4 && DT == HDP_BF16;
-  constexpr int ES = DT == HDP_F32 ? 4 : 2;
-  const int n = ga.n;
-  const std::vector<std::vector<int>> sets = SPLIT_B ? std::vector<std::vector<int>>{} : shared_x_sets(ga);
-  const bool fuse = !sets.empty();
-  std::vector<int> set_of(n, -1), blk0(n, 0);
-  for (int k = 0; k < (int)sets.size(); ++k)
-    for (int m = 0; m < (int)sets[k].size(); ++m) {
-      set_of[sets[k][m]] = k;
-      blk0[sets[k][m]] = m * RB;
-    }
-  std::vector<SweepDesc> sd[3];
-  std::vector<YRedDesc> yd[2];
-  std::vector<FinDesc> fd(n);
-  std::vector<char> s1x(n);
-  std::vector<int> at_c(n, -1), at_b(n, -1);  // each module's X / G side: index in its OUTER phase
-  int64_t U[3] = {0, 0, 0};
-  double bytes_ph[3] = {0, 0, 0}, flop_ph[3] = {0, 0, 0};
-  auto add = [&](int ph, SweepDesc d) {
-    d.pre = U[ph];
-    U[ph] += (int64_t)d.nct * d.S;
-    int rows = 0;
-    for (int b = 0; b < d.nb && b < kSwMaxBlk; ++b) rows += d.rbr[b];
-    bytes_ph[ph] += (double)ES * d.T * d.N;
-    flop_ph[ph] += 2.0 * d.T * d.N * (fuse && (ph != 1) ? rows : d.r) * (ph == 1 && !SPLIT_B ? 2.0 : 1.0);
-    sd[ph].push_back(d);
-    return (int)sd[ph].size() - 1;
-  };
-  for (int k = 0; k < 2; ++k) yd[k].resize(n);
-  int64_t yblk = 1;
-  bool v4 = true;  // 4 elements per finish thread when every module allows it
-  for (int i = 0; i < n; ++i) {
-    const ProbeDesc& p = ga.d[i];
-    const int S = (int)((p.T + 15) / 16);
-    const int si = set_of[i];
-    s1x[i] = si >= 0 ? 1 : (p.in <= p.out);  // S1 = the smaller stream, read twice (a set: its X)
-    SweepDesc x = side_desc(p, true, RB, S), gg = side_desc(p, false, RB, S);
-    if (si >= 0) {
-      const ProbeDesc& lead = ga.d[sets[si][0]];
-      // this module's G side reads its H in phase B: member m's [T][16 lanes][RB] slice of the set's
-      // H buffer (lead's yH, rows of 64 floats: the plain layout per member, member-major)
-      gg.y_in = lead.yH + 16 * blk0[i];
-      gg.yrs = 4 * 16;
-      if (sets[si][0] == i) {  // the set's X side (phases A and C), r-blocks of every member
-        SweepDesc fx = x;
-        fx.nb = RB * (int)sets[si].size();
-        fx.y_in = lead.yJ;  // the set's padded J (phase C)
-        fx.yrs = 4 * 16;
-        fx.yls = 4;
-        for (int m = 0; m < (int)sets[si].size(); ++m) {
-          const SweepDesc xm = side_desc(ga.d[sets[si][m]], true, RB, S);
-          for (int bb = 0; bb < RB; ++bb) {
-            const int b = m * RB + bb;
-            fx.Fb[b] = xm.Fb[bb];
-            fx.rbr[b] = xm.rbr[bb];
-            fx.slab_b[b] = xm.slab_b[bb];
-            fx.part_b[b] = xm.part_b[bb];
-            fx.gb[b] = xm.gb[bb];
-            fx.sc[b] = xm.sc[bb];
-            fx.accb[b] = xm.accb[bb];
-          }
-        }
-        add(0, fx);
-        at_c[i] = add(2, fx);
-        for (int m : sets[si]) at_c[m] = at_c[i];
-      }
-      at_b[i] = add(1, gg);
-    } else {
-      const SweepDesc& d1 = s1x[i] ? x : gg;
-      SweepDesc d2 = s1x[i] ? gg : x;
-      SweepDesc d1c = d1;
-      if (fuse) {  // phase C runs the FUSE instance: Y_S2 in the padded layout
-        d1c.yrs = 4 * 16;
-        d1c.yls = 4;
-      }
-      add(0, d1);
-      if (SPLIT_B) {  // S2's OUTER, right after S1's in phase C
-        add(1, d2);
-        const int c1 = add(2, d1c);
-        const int c2 = add(2, d2);
-        at_c[i] = s1x[i] ? c1 : c2;  // X side
-        at_b[i] = s1x[i] ? c2 : c1;  // G side (both in phase C)
-      } else {
-        const int bi = add(1, d2);
-        const int ci = add(2, d1c);
-        at_c[i] = s1x[i] ? ci : bi;
-        at_b[i] = s1x[i] ? bi : ci;
-      }
-    }
-    // R1: S1's slabs -> the projection phase B reads; R2: S2's slabs -> the one phase C reads
-    if (si >= 0) {
-      const ProbeDesc& lead = ga.d[sets[si][0]];
-      yd[0][i] = YRedDesc{p.slabH, lead.yH + 16 * blk0[i], p.T, p.ksh, 4 * 16, RB, 0};
-      yd[1][i] = YRedDesc{p.slabJ, lead.yJ + blk0[i], p.T, p.ksj, 4 * 16, 4, 0};
-    } else {
-      const SweepDesc& d1 = s1x[i] ? x : gg;
-      const SweepDesc& d2 = s1x[i] ? gg : x;
-      yd[0][i] = YRedDesc{d1.slab_out, s1x[i] ? p.yH : p.yJ, p.T, d1.nct, rp, RB, 0};
-      yd[1][i] = YRedDesc{d2.slab_out, s1x[i] ? p.yJ : p.yH, p.T, d2.nct, fuse ? 4 * 16 : rp, fuse ? 4 : RB, 0};
-    }
-    const int64_t yb = (p.T * rp / 4 + 255) / 256;
-    yblk = yb > yblk ? yb : yblk;
-    fd[i] = FinDesc{p.gA, p.gB, (int)p.in, (int)p.out, p.r, p.accumulate, p.scale, p.ldb, {}, {}};
-    v4 = v4 && p.r % 4 == 0 && p.ldb % 4 == 0 && p.in % 4 == 0 && (reinterpret_cast<uintptr_t>(p.gA) & 15) == 0 &&
-         (reinterpret_cast<uintptr_t>(p.gB) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.partA) & 15) == 0 &&
-         (reinterpret_cast<uintptr_t>(p.partB) & 15) == 0;
-  }
-  const int V = v4 ? 4 : 1;
-  const size_t proj_lds =
+  constexpr bool BF = DT == HDP_BF16;
+  constexpr bool SPLIT_B = RB >= 4 && BF;  // SweepSides::split_b
+  constexpr size_t proj_lds =
       ((size_t)kSwWaves * 16 * kTileLd + (size_t)sw_nbuf<RB>() * kSwWaves * 16 * rp) * sizeof(float) +
       2 * sw_nbuf<RB>() * 4;
-  const size_t fuse_lds =
+  constexpr size_t fuse_lds =
       ((size_t)kSwWaves * 16 * kTileLd + (size_t)sw_nbuf<kSwMaxBlk, true>() * kSwWaves * 16 * 16 * kSwMaxBlk) *
           sizeof(float) +
       2 * sw_nbuf<kSwMaxBlk, true>() * 4;
   constexpr int OCC_B = SPLIT_B ? 1 : RB >= 4 ? 3 : VEC ? 2 : 1;
   constexpr int MODE_B = SPLIT_B ? kSwProj : kSwProj | kSwOuter;
-  constexpr int RBF = RB <= 2 ? kSwMaxBlk : RB;  // the FUSE instances' r-blocks (only built for RB <= 2)
+  constexpr bool CAN_FUSE = RB <= 2;                 // the FUSE instances are only built for r-block <= 2,
+  constexpr int RBF = CAN_FUSE ? kSwMaxBlk : RB;     // as 4 r-block templates
   // bf16 activations: the PROJ-only and OUTER-only phases on 16x16x32 bf16 MFMA (K32; env
   // HDP_PROBE_K32=0 keeps the 16x16x16 forms)
-  constexpr bool BF = DT == HDP_BF16;
   // (every r-block: r03 restricted them to r-block 4 after wrong projections at r <= 32, whose cause was an
   // MFMA result read 3 wait states after issue behind a taken branch -- HDP_MFMA_FENCE, r04;
   // tests/test_gpu_kernels.py::test_probe_k32_all_rblocks)
-  const int k32m = BF ? probe_k32() : 0;
+  const int k32m = BF ? kn.k32 : 0;
   const bool k32 = k32m >= 2 || (k32m == 1 && RB >= 4);
   const bool k32c = k32m == 3 || (k32m >= 1 && RB >= 4);  // the OUTER phase (C)
   // phase A's FUSE instance (4 r-block template) on float32 activations: X6 (the K32 PROJ form on split
   // activations; phase C's X6 OUTER form spills at 256 VGPRs beside four load sets: kept on f32 MFMA)
-  const bool x6 = !BF && fuse && probe_x6();
+  const bool x6 = !BF && fuse && kn.x6;
   const bool kf = k32 || x6;  // phase A's K32 template (bf16 split fragments / X6)
-  int G[3];
-  if (fuse) {
-    if constexpr (RB <= 2) {
-      G[0] = kf ? phase_grid<DT, RBF, kSwProj, VEC, 1, true, true>(U[0], fuse_lds)
-                : phase_grid<DT, RBF, kSwProj, VEC, 1, true>(U[0], fuse_lds);
-      G[2] = k32 ? phase_grid<DT, RBF, kSwOuter, VEC, 1, true, BF>(U[2], 0)  // (the FUSE instance is r-block 4)
-                 : phase_grid<DT, RBF, kSwOuter, VEC, 1, true>(U[2], 0);
-    }
-  } else {
-    G[0] = k32 ? phase_grid<DT, RB, kSwProj, VEC, 1, false, BF>(U[0], proj_lds)
-               : phase_grid<DT, RB, kSwProj, VEC, 1>(U[0], proj_lds);
-    G[2] = k32c ? phase_grid<DT, RB, kSwOuter, VEC, 1, false, BF>(U[2], 0)
-               : phase_grid<DT, RB, kSwOuter, VEC, 1>(U[2], 0);
-  }
+  const bool fused = CAN_FUSE && fuse;
   constexpr bool K32B = BF && MODE_B == kSwProj;  // phase B is PROJ-only on the split (r-block 4) path
-  G[1] = k32 ? phase_grid<DT, RB, MODE_B, VEC, OCC_B, false, K32B>(U[1], proj_lds)
-             : phase_grid<DT, RB, MODE_B, VEC, OCC_B>(U[1], proj_lds);
-  HDP_CHECK_ARG(G[0] <= 4096 && G[1] <= 4096 && G[2] <= 4096, "probe sweep: grid above the table size");
-  HDP_CHECK_ARG(yblk < 65536 && n < 65536, "probe sweep: group too large");
-  // the workgroups' ranges: cost-weighted in phase A of a float32 shared-X group, equal steps elsewhere
-  std::vector<int64_t> bounds[3];
-  const bool weighted = fuse && !BF && probe_balance();
-  for (int ph = 0; ph < 3; ++ph) {
-    HDP_CHECK_ARG(U[ph] < (1ll << 31), "probe sweep: too many steps in one phase");
-    G[ph] = phase_ranges(sd[ph], G[ph], weighted && ph == 0 ? kSwWeightA : nullptr, bounds[ph]);
-    // memory safety: a stripe's piece buffer holds sweep_kmax pieces, which is what ranges of >= kSwMinSteps
-    // steps can produce (a single workgroup may hold fewer: one piece per stripe)
-    const int64_t least = U[ph] < kSwMinSteps ? U[ph] : kSwMinSteps;
-    bool ok = (int)bounds[ph].size() == G[ph] + 1 && bounds[ph][0] == 0 && bounds[ph][G[ph]] == U[ph];
-    for (int w = 0; ok && w < G[ph]; ++w) ok = bounds[ph][w + 1] - bounds[ph][w] >= least;
-    HDP_CHECK_ARG(ok, "probe sweep: a workgroup range below the minimum step count");
+  // (A, B, C in launch order: the device code keeps its order of instances)
+  if (fused) {
+    if constexpr (CAN_FUSE)
+      pk[0] = {kf ? probe_sweep_kernel<DT, RBF, kSwProj, VEC, 1, true, true>
+                  : probe_sweep_kernel<DT, RBF, kSwProj, VEC, 1, true>,
+               fuse_lds};
+  } else {
+    pk[0] = {k32 ? probe_sweep_kernel<DT, RB, kSwProj, VEC, 1, false, BF> : probe_sweep_kernel<DT, RB, kSwProj, VEC, 1>,
+             proj_lds};
   }
-  // finish: the pieces of X's OUTER and of G's (SwFinishSide::ph 0 = phase B, 1 = C); every
-  // module's pieces are in its own part buffers (a shared-X set's OUTER writes each member's rows there)
-  for (int i = 0; i < n; ++i) {
-    const ProbeDesc& p = ga.d[i];
-    const bool x_in_c = SPLIT_B || s1x[i], g_in_c = SPLIT_B || !s1x[i];
-    const SweepDesc& dx = sd[x_in_c ? 2 : 1][at_c[i]];
-    const SweepDesc& dg = sd[g_in_c ? 2 : 1][at_b[i]];
-    fd[i].sx = SwFinishSide{p.partA, dx.pre, dx.S, dx.kmax, x_in_c ? 1 : 0, 0};
-    fd[i].sg = SwFinishSide{p.partB, dg.pre, dg.S, dg.kmax, g_in_c ? 1 : 0, 0};
+  pk[1] = {k32 ? probe_sweep_kernel<DT, RB, MODE_B, VEC, OCC_B, false, K32B>
+               : probe_sweep_kernel<DT, RB, MODE_B, VEC, OCC_B>,
+           proj_lds};
+  if (fused) {
+    if constexpr (CAN_FUSE)
+      pk[2] = {k32 ? probe_sweep_kernel<DT, RBF, kSwOuter, VEC, 1, true, BF>  // (the FUSE instance is r-block 4)
+                   : probe_sweep_kernel<DT, RBF, kSwOuter, VEC, 1, true>,
+               0};
+  } else {
+    pk[2] = {k32c ? probe_sweep_kernel<DT, RB, kSwOuter, VEC, 1, false, BF> : probe_sweep_kernel<DT, RB, kSwOuter, VEC, 1>,
+             0};
   }
-  // one blob: [sd A | sd B | sd C | wst A | wst B | wst C | bnd A | bnd B | bnd C | yd R1 | yd R2 | fd]
-  size_t off = 0;
-  auto place = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  size_t o_sd[3], o_w[3], o_b[3], o_y[2];
-  for (int ph = 0; ph < 3; ++ph) o_sd[ph] = place(sizeof(SweepDesc) * sd[ph].size());
-  for (int ph = 0; ph < 3; ++ph) o_w[ph] = place(sizeof(int) * 4 * G[ph]);
-  for (int ph = 0; ph < 3; ++ph) o_b[ph] = place(sizeof(int) * (G[ph] + 1));
-  for (int k = 0; k < 2; ++k) o_y[k] = place(sizeof(YRedDesc) * n);
-  const size_t o_f = place(sizeof(FinDesc) * n);
-  // the finish's jobs: the stripes that more than one workgroup segment covered (the others wrote their
-  // gradient blocks in phase B / C)
-  std::vector<int> jobs;
-  double pieces = 0;
-  {
-    for (int i = 0; i < n; ++i) {
-      const ProbeDesc& p = ga.d[i];
-      for (int side = 0; side < 2; ++side) {
-        const SwFinishSide& sd2 = side == 0 ? fd[i].sx : fd[i].sg;
-        const int nct = side == 0 ? p.ksh : p.ksj;
-        const int ph = sd2.ph + 1;  // phase B = 1, C = 2
-        for (int ct = 0; ct < nct; ++ct) {
-          const int64_t u0 = sd2.pre + (int64_t)ct * sd2.S;
-          const int np = plan_owner(bounds[ph], u0 + sd2.S - 1) - plan_owner(bounds[ph], u0) + 1;
-          if (np > 1) {
-            HDP_CHECK_ARG(np <= sd2.kmax, "probe sweep: a stripe has more pieces than its buffer holds");
-            jobs.push_back(i);
-            jobs.push_back(2 * ct + side);
-            jobs.push_back(np);
-            jobs.push_back(0);
-            // the finish reads the pieces and updates the gradient of split stripes only
-            pieces += 4.0 * p.r * kSwC * ((double)np + (p.accumulate ? 2 : 1));
-          }
-        }
-      }
-    }
+}
+
+// resident 512-thread workgroups of one sweep kernel instance x CUs (cached per instance and device)
+static int sweep_slots(const SweepKernel& k) {
+  struct Entry {
+    void (*fn)(SweepArgs);
+    int dev, slots;
+  };
+  static std::mutex mu;
+  static std::vector<Entry> cache;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
+  std::lock_guard<std::mutex> lk(mu);
+  for (const Entry& e : cache)
+    if (e.fn == k.fn && e.dev == dev) return e.slots;
+  int cus = 0, per = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k.fn, 512, k.lds) != hipSuccess || per <= 0) per = 1;
+  cache.push_back(Entry{k.fn, dev, cus * per});
+  return cus * per;
+}
+
+// knobs -> sides (plan_sweep_sides) -> the phases' instances and their resident workgroups -> tables
+// (plan_sweep_tables) -> upload -> A, R1, B, R2, C, finish; `tab` = the group's device table region
+template <int DT, int RB, bool VEC>
+static int launch_sweep(const HostGroup& ga, char* tab, hipStream_t st) {
+  constexpr int rp = 16 * RB;
+  const int n = ga.n;
+  const SweepKnobs kn = sweep_knobs();
+  SweepSides s;
+  plan_sweep_sides(ga, DT == HDP_BF16, kn, s);
+  SweepKernel pk[3];
+  pick_sweep<DT, RB, VEC>(s.fuse, kn, pk);
+  const int slots[3] = {sweep_slots(pk[0]), sweep_slots(pk[1]), sweep_slots(pk[2])};
+  SweepTables t;
+  const SweepError pe = plan_sweep_tables(ga, s, slots, t);
+  static_assert(kSweepEInval == HDP_EINVAL, "the planner's error code");
+  if (pe.code != 0) {
+    set_error("%s", pe.msg);
+    return pe.code;
   }
-  const int njobs = (int)(jobs.size() / 4);
-  HDP_CHECK_ARG((int64_t)njobs * (rp * kSwC / 256) < (1ll << 31), "probe sweep: finish grid too large");
-  const size_t o_j = place(sizeof(int) * jobs.size());
-  size_t tab_cap = kTableFixed + (size_t)n * table_per_module();
-  for (int i = 0; i < n; ++i) tab_cap += finish_jobs_bytes(ga.d[i].in, ga.d[i].out);
-  HDP_CHECK_ARG(off <= tab_cap, "probe sweep: descriptor tables exceed their space");
-  std::vector<char> blob(off);
-  for (int ph = 0; ph < 3; ++ph) {
-    memcpy(blob.data() + o_sd[ph], sd[ph].data(), sizeof(SweepDesc) * sd[ph].size());
-    phase_starts(sd[ph], bounds[ph], G[ph], reinterpret_cast<int*>(blob.data() + o_w[ph]),
-                 reinterpret_cast<int*>(blob.data() + o_b[ph]));
-  }
-  for (int k = 0; k < 2; ++k) memcpy(blob.data() + o_y[k], yd[k].data(), sizeof(YRedDesc) * n);
-  memcpy(blob.data() + o_f, fd.data(), sizeof(FinDesc) * n);
-  if (njobs) memcpy(blob.data() + o_j, jobs.data(), sizeof(int) * jobs.size());
-  int rc = probe_tables_upload(blob, tab, st);
+  const int rc = probe_tables_upload(t.blob, tab, st);
   if (rc) return rc;
 
   int* err = probe_err_word();
   HDP_CHECK_ARG(err != nullptr, "probe sweep: error word allocation failed");
   int* errd = probe_err_local();
   const int spin = probe_spin();
-  SweepArgs sa[3];
-  for (int ph = 0; ph < 3; ++ph)
-    sa[ph] = SweepArgs{(int)sd[ph].size(), G[ph], spin, U[ph], err, errd, reinterpret_cast<const SweepDesc*>(tab + o_sd[ph]),
-                       reinterpret_cast<const int*>(tab + o_w[ph]), reinterpret_cast<const int*>(tab + o_b[ph])};
-  // workspace bytes the reduce / finish passes move (slabs + Y; pieces + gradients) -- counted
-  // as algorithmic for these launches: they are the price of the stripe decomposition
-  double slab[2] = {0, 0};
-  for (int i = 0; i < n; ++i)
-    for (int k = 0; k < 2; ++k) slab[k] += 4.0 * ga.d[i].T * rp * (yd[k][i].nct + 1);
-  auto reduce = [&](int k) {
-    KTimer kt(K_PROBE_REDUCE, st, slab[k]);
-    hipLaunchKernelGGL(probe_yreduce_kernel, dim3((unsigned)yblk, (unsigned)n), dim3(256), 0, st,
-                       YReduceArgs{n, rp, reinterpret_cast<const YRedDesc*>(tab + o_y[k])});
+  static const int kid[3] = {K_SWEEP_A, K_SWEEP_B, K_SWEEP_C};
+  auto sweep = [&](int ph) {
+    const SweepArgs sa{(int)s.sd[ph].size(), t.G[ph], spin, s.U[ph], err, errd,
+                       reinterpret_cast<const SweepDesc*>(tab + t.o_sd[ph]), reinterpret_cast<const int*>(tab + t.o_w[ph]),
+                       reinterpret_cast<const int*>(tab + t.o_b[ph])};
+    KTimer kt(kid[ph], st, s.bytes_ph[ph], s.flop_ph[ph]);
+    hipLaunchKernelGGL(pk[ph].fn, dim3(t.G[ph]), dim3(512), pk[ph].lds, st, sa);
   };
-  {
-    KTimer kt(K_SWEEP_A, st, bytes_ph[0], flop_ph[0]);
-    if (fuse) {
-      if constexpr (RB <= 2) {
-        if (kf)
-          hipLaunchKernelGGL((probe_sweep_kernel<DT, RBF, kSwProj, VEC, 1, true, true>), dim3(G[0]), dim3(512), fuse_lds,
-                             st, sa[0]);
-        else
-          hipLaunchKernelGGL((probe_sweep_kernel<DT, RBF, kSwProj, VEC, 1, true>), dim3(G[0]), dim3(512), fuse_lds, st,
-                             sa[0]);
-      }
-    } else if (k32) {
-      hipLaunchKernelGGL((probe_sweep_kernel<DT, RB, kSwProj, VEC, 1, false, BF>), dim3(G[0]), dim3(512), proj_lds, st,
-                         sa[0]);
-    } else {
-      hipLaunchKernelGGL((probe_sweep_kernel<DT, RB, kSwProj, VEC, 1>), dim3(G[0]), dim3(512), proj_lds, st, sa[0]);
-    }
-  }
+  auto reduce = [&](int k) {
+    KTimer kt(K_PROBE_REDUCE, st, s.slab[k]);
+    hipLaunchKernelGGL(probe_yreduce_kernel, dim3((unsigned)s.yblk, (unsigned)n), dim3(256), 0, st,
+                       YReduceArgs{n, rp, reinterpret_cast<const YRedDesc*>(tab + t.o_y[k])});
+  };
+  sweep(0);
   HDP_CHECK_LAUNCH();
   reduce(0);
   HDP_CHECK_LAUNCH();
-  {
-    KTimer kt(K_SWEEP_B, st, bytes_ph[1], flop_ph[1]);
-    if (k32)
-      hipLaunchKernelGGL((probe_sweep_kernel<DT, RB, MODE_B, VEC, OCC_B, false, K32B>), dim3(G[1]), dim3(512), proj_lds,
-                         st, sa[1]);
-    else
-      hipLaunchKernelGGL((probe_sweep_kernel<DT, RB, MODE_B, VEC, OCC_B>), dim3(G[1]), dim3(512), proj_lds, st, sa[1]);
-  }
+  sweep(1);
   HDP_CHECK_LAUNCH();
   reduce(1);
   HDP_CHECK_LAUNCH();
-  {
-    KTimer kt(K_SWEEP_C, st, bytes_ph[2], flop_ph[2]);
-    if (fuse) {
-      if constexpr (RB <= 2) {
-        if (k32)
-          hipLaunchKernelGGL((probe_sweep_kernel<DT, RBF, kSwOuter, VEC, 1, true, BF>), dim3(G[2]), dim3(512), 0, st,
-                             sa[2]);
-        else
-          hipLaunchKernelGGL((probe_sweep_kernel<DT, RBF, kSwOuter, VEC, 1, true>), dim3(G[2]), dim3(512), 0, st, sa[2]);
-      }
-    } else if (k32c) {
-      hipLaunchKernelGGL((probe_sweep_kernel<DT, RB, kSwOuter, VEC, 1, false, BF>), dim3(G[2]), dim3(512), 0, st, sa[2]);
-    } else {
-      hipLaunchKernelGGL((probe_sweep_kernel<DT, RB, kSwOuter, VEC, 1>), dim3(G[2]), dim3(512), 0, st, sa[2]);
-    }
-  }
+  sweep(2);
   HDP_CHECK_LAUNCH();
-  if (njobs) {  // (none when every stripe had one segment: no launch)
+  if (t.njobs) {  // (none when every stripe had one segment: no launch)
+    const int V = s.v4 ? 4 : 1;
     const int bx = (rp * kSwC + 256 * V - 1) / (256 * V);
-    SwFinishArgs fa{n, rp, reinterpret_cast<const FinDesc*>(tab + o_f),
-                    reinterpret_cast<const int*>(tab + o_j), bx};
-    KTimer kt(K_PROBE_FINISH, st, pieces);
-    if (v4)
-      hipLaunchKernelGGL(probe_sweep_finish_kernel<4>, dim3((unsigned)(njobs * bx)), dim3(256), 0, st, fa);
+    SwFinishArgs fa{n, rp, reinterpret_cast<const FinDesc*>(tab + t.o_f), reinterpret_cast<const int*>(tab + t.o_j), bx};
+    KTimer kt(K_PROBE_FINISH, st, t.pieces);
+    if (s.v4)
+      hipLaunchKernelGGL(probe_sweep_finish_kernel<4>, dim3((unsigned)(t.njobs * bx)), dim3(256), 0, st, fa);
     else
-      hipLaunchKernelGGL(probe_sweep_finish_kernel<1>, dim3((unsigned)(njobs * bx)), dim3(256), 0, st, fa);
+      hipLaunchKernelGGL(probe_sweep_finish_kernel<1>, dim3((unsigned)(t.njobs * bx)), dim3(256), 0, st, fa);
     HDP_CHECK_LAUNCH();
   }
   return HDP_OK;
@@ -2232,11 +1836,23 @@ extern "C" int hdp_probe_grads_group(int n, const hdp_probe_item* items, int x_d
     }
     return HDP_OK;
   }
+  const bool sweep = slicing || use_sweep(rb_of(items[0].r));  // (slices always run the sweep)
+  if (!sweep && n > kMaxSplit) {
+    // the split path's kernel arguments hold kMaxSplit modules: launch in stream-ordered
+    // chunks that reuse the workspace from its start
+    for (int k = 0; k < n; k += kMaxSplit) {
+      const int rc = hdp_probe_grads_group(n - k < kMaxSplit ? n - k : kMaxSplit, items + k, x_dtype, workspace,
+                                           workspace_bytes, stream);
+      if (rc != HDP_OK) return rc;
+    }
+    return HDP_OK;
+  }
+  // one launch set from here on: no two of the caller's items may write the same gradient
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < i; ++k)
+      HDP_CHECK_ARG(items[k].gA != items[i].gA && items[k].gB != items[i].gB,
+                    "hdp_probe_grads_group: items %d and %d accumulate into the same gradient", k, i);
   if (slicing) {
-    for (int i = 0; i < n; ++i)
-      for (int k = 0; k < i; ++k)
-        HDP_CHECK_ARG(items[k].gA != items[i].gA && items[k].gB != items[i].gB,
-                      "hdp_probe_grads_group: items %d and %d accumulate into the same gradient", k, i);
     for (int i = 0; i < n; ++i) {
       const hdp_probe_item& it = items[i];
       const int ns = n_slices(it.r), rk = (it.r + ns - 1) / ns;
@@ -2256,17 +1872,6 @@ extern "C" int hdp_probe_grads_group(int n, const hdp_probe_item* items, int x_d
     n = (int)sliced.size();
     items = sliced.data();
   }
-  const bool sweep = slicing || use_sweep(rb_of(items[0].r));
-  if (!sweep && n > kMaxSplit) {
-    // the split path's kernel arguments hold kMaxSplit modules: launch in stream-ordered
-    // chunks that reuse the workspace from its start
-    for (int k = 0; k < n; k += kMaxSplit) {
-      const int rc = hdp_probe_grads_group(n - k < kMaxSplit ? n - k : kMaxSplit, items + k, x_dtype, workspace,
-                                           workspace_bytes, stream);
-      if (rc != HDP_OK) return rc;
-    }
-    return HDP_OK;
-  }
   hipStream_t st = as_stream(stream);
   HostGroup ga;
   ga.RB = slicing ? 4 : rb_of(items[0].r);
@@ -2274,19 +1879,9 @@ extern "C" int hdp_probe_grads_group(int n, const hdp_probe_item* items, int x_d
   ga.d.reserve(n);
   char* ws = reinterpret_cast<char*>(workspace);
   // the group's descriptor tables first (sweep path), then the modules' work areas
-  size_t tab_bytes = 0;
-  if (sweep) {
-    tab_bytes = kTableFixed + (size_t)n * table_per_module();
-    for (int i = 0; i < n; ++i) tab_bytes += finish_jobs_bytes(items[i].in, items[i].out);
-  }
-  size_t off = tab_bytes;
+  size_t off = sweep ? sweep_table_bytes(items, n) : 0;
   HDP_CHECK_ARG(!sweep || off <= workspace_bytes, "hdp_probe_grads: workspace %zu bytes too small (need %zu)",
                 workspace_bytes, off);
-  if (!slicing)
-    for (int i = 0; i < n; ++i)
-      for (int k = 0; k < i; ++k)
-        HDP_CHECK_ARG(items[k].gA != items[i].gA && items[k].gB != items[i].gB,
-                      "hdp_probe_grads_group: items %d and %d accumulate into the same gradient", k, i);
   for (int i = 0; i < n; ++i) {
     const hdp_probe_item& it = items[i];
     HDP_CHECK_ARG(it.in > 0 && it.out > 0 && it.r > 0 && it.T >= 0, "hdp_probe_grads: bad shape (item %d)", i);
@@ -2321,12 +1916,7 @@ extern "C" int hdp_probe_grads_group(int n, const hdp_probe_item* items, int x_d
     d.B = it.B;
     d.gA = it.gA;
     d.gB = it.gB;
-    d.slabH = reinterpret_cast<float*>(ws + off + p.off_slabH);
-    d.slabJ = reinterpret_cast<float*>(ws + off + p.off_slabJ);
-    d.partA = reinterpret_cast<float*>(ws + off + p.off_partA);
-    d.partB = reinterpret_cast<float*>(ws + off + p.off_partB);
-    d.yH = reinterpret_cast<float*>(ws + off + p.off_yH);
-    d.yJ = reinterpret_cast<float*>(ws + off + p.off_yJ);
+    place_module(d, p, ws + off);
     d.T = it.T;
     d.in = it.in;
     d.out = it.out;
@@ -2334,11 +1924,6 @@ extern "C" int hdp_probe_grads_group(int n, const hdp_probe_item* items, int x_d
     d.r = it.r;
     d.b_t = it.b_transposed ? 1 : 0;
     d.accumulate = it.accumulate ? 1 : 0;
-    d.ksh = p.ksh;
-    d.ksj = p.ksj;
-    d.kst = p.kst;
-    d.colh = p.colh;
-    d.colj = p.colj;
     d.ldb = ldb;
     off += mod_bytes;
     ga.d.push_back(d);

@@ -56,12 +56,9 @@ def variant(src, v):
         rep("""  constexpr int OCC_B = SPLIT_B ? 1 : RB >= 4 ? 3 : VEC ? 2 : 1;""",
             """  constexpr int OCC_B = SPLIT_B ? 1 : RB >= 4 ? 3 : 1;""")
     elif v == "x6c":  # (a candidate) float32 phase C on the X6 OUTER form (pairs of steps, four load sets; spills)
-        rep("""      G[2] = k32 ? phase_grid<DT, RBF, kSwOuter, VEC, 1, true, BF>(U[2], 0)""",
-            """      G[2] = kf ? phase_grid<DT, RBF, kSwOuter, VEC, 1, true, true>(U[2], 0)""")
-        rep("""        if (k32)
-          hipLaunchKernelGGL((probe_sweep_kernel<DT, RBF, kSwOuter, VEC, 1, true, BF>), dim3(G[2]), dim3(512), 0, st,""",
-            """        if (kf)
-          hipLaunchKernelGGL((probe_sweep_kernel<DT, RBF, kSwOuter, VEC, 1, true, true>), dim3(G[2]), dim3(512), 0, st,""")
+        # (pick_sweep: the one place that names phase C's instance, for the occupancy query and the launch)
+        rep("""      pk[2] = {k32 ? probe_sweep_kernel<DT, RBF, kSwOuter, VEC, 1, true, BF>""",
+            """      pk[2] = {kf ? probe_sweep_kernel<DT, RBF, kSwOuter, VEC, 1, true, true>""")
     elif v == "ntz":
         rep("""            z[p] = load4<DT>(Zb + zo[p], 0);""", """            z[p] = load4_nt<DT>(Zb + zo[p], 0);""")
     else:
