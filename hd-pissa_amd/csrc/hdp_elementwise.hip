@@ -177,6 +177,102 @@ __global__ __launch_bounds__(kEwThreads) void fold_bf16_kernel(const float* __re
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Grouped contiguous copy (hdp_copy_group): the shard exchange's pack (own W rows -> send buffer) and
+// scatter (the other ranks' rows -> W) as one launch over {dst, src, bytes} ranges.  merge_chunk_kernel's
+// form without the arithmetic: one flat chunk space over the items, a workgroup owns kCopyU x 256
+// consecutive 16-byte vectors at a time, every load of the chunk issued before its first store,
+// non-temporal both ways (each byte touched once).  An item whose dst and src sit alike within 16 bytes
+// is split into head bytes up to dst's next 16-byte boundary, whole vectors, and tail bytes; the lanes of
+// the item's first chunk copy the (at most 15 + 15) head and tail bytes one by one.  An item whose
+// pointers sit differently is copied byte by byte over the same chunk walk.
+// ---------------------------------------------------------------------------------------
+constexpr int kCopyU = 8;             // vectors per lane per chunk
+constexpr int kCopyGroupMax = 170;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+struct CopyGroupArgs {
+  int n;
+  hdp_copy_item it[kCopyGroupMax];
+};
+static_assert(sizeof(CopyGroupArgs) <= 4096, "copy group kernel arguments must stay within 4 KB");
+constexpr int64_t kCopyChunk = (int64_t)kEwThreads * kCopyU;  // vectors (aligned item) per chunk
+
+// the split of one item (bytes > 0): head bytes, whole vectors and the chunks it owns; vec = false for an
+// item copied byte by byte (a chunk is then kCopyChunk * 16 bytes)
+struct CopySplit {
+  bool vec;
+  int64_t head, nv, nch;
+};
+__host__ __device__ inline CopySplit copy_split(const void* dst, const void* src, int64_t bytes) {
+  CopySplit s;
+  const uintptr_t d = reinterpret_cast<uintptr_t>(dst), q = reinterpret_cast<uintptr_t>(src);
+  s.vec = ((d ^ q) & 15u) == 0;
+  if (s.vec) {
+    const int64_t h = (int64_t)((16u - (d & 15u)) & 15u);
+    s.head = h < bytes ? h : bytes;
+    s.nv = (bytes - s.head) >> 4;
+    s.nch = s.nv ? (s.nv + kCopyChunk - 1) / kCopyChunk : 1;  // (head / tail only: still one chunk)
+  } else {
+    s.head = 0;
+    s.nv = 0;
+    s.nch = (bytes + kCopyChunk * 16 - 1) / (kCopyChunk * 16);
+  }
+  return s;
+}
+
+__global__ __launch_bounds__(kEwThreads) void copy_chunk_kernel(CopyGroupArgs ga) {
+  int it = 0;
+  CopySplit sp = copy_split(ga.it[0].dst, ga.it[0].src, ga.it[0].bytes);
+  int64_t base = 0;                                     // item it owns chunks [base, base + sp.nch)
+  for (int64_t c = blockIdx.x;; c += gridDim.x) {      // c, it, base, sp: workgroup-uniform
+    while (c >= base + sp.nch) {
+      base += sp.nch;
+      if (++it == ga.n) return;
+      sp = copy_split(ga.it[it].dst, ga.it[it].src, ga.it[it].bytes);
+    }
+    const int64_t bytes = ga.it[it].bytes;
+    HDP_GLOBAL uint8_t* D1 = gptr(reinterpret_cast<uint8_t*>(ga.it[it].dst));
+    const HDP_GLOBAL uint8_t* S1 = gptr(reinterpret_cast<const uint8_t*>(ga.it[it].src));
+    if (sp.vec) {
+      HDP_GLOBAL u32x4* D4 = reinterpret_cast<HDP_GLOBAL u32x4*>(D1 + sp.head);
+      const HDP_GLOBAL u32x4* S4 = reinterpret_cast<const HDP_GLOBAL u32x4*>(S1 + sp.head);
+      const int64_t v0 = (c - base) * kCopyChunk + threadIdx.x;
+      u32x4 x[kCopyU];
+#pragma unroll
+      for (int u = 0; u < kCopyU; ++u) {
+        const int64_t i = v0 + u * kEwThreads;
+        if (i < sp.nv) x[u] = __builtin_nontemporal_load(S4 + i);
+      }
+#pragma unroll
+      for (int u = 0; u < kCopyU; ++u) {
+        const int64_t i = v0 + u * kEwThreads;
+        if (i < sp.nv) __builtin_nontemporal_store(x[u], D4 + i);
+      }
+      if (c == base) {  // the item's first chunk: head bytes on lanes 0-15, tail bytes on lanes 16-31
+        const int64_t t0 = sp.head + 16 * sp.nv;
+        const int l = threadIdx.x;
+        if (l < sp.head) D1[l] = S1[l];
+        else if (l >= 16 && l < 32 && t0 + (l - 16) < bytes) D1[t0 + (l - 16)] = S1[t0 + (l - 16)];
+      }
+    } else {
+      const int64_t b0 = (c - base) * kCopyChunk * 16 + threadIdx.x;
+      uint8_t x[2 * kCopyU];
+      for (int64_t o = 0; o < kCopyChunk * 16; o += (int64_t)kEwThreads * 2 * kCopyU) {
+#pragma unroll
+        for (int u = 0; u < 2 * kCopyU; ++u) {
+          const int64_t i = b0 + o + u * kEwThreads;
+          if (i < bytes) x[u] = S1[i];
+        }
+#pragma unroll
+        for (int u = 0; u < 2 * kCopyU; ++u) {
+          const int64_t i = b0 + o + u * kEwThreads;
+          if (i < bytes) D1[i] = x[u];
+        }
+      }
+    }
+  }
+}
+
 static int merge_chunk_launch(const MergeGroupArgs& ga, bool bf16, double bytes, hipStream_t st) {
   // the chunk the kernel walks (merge_chunk_kernel<BF>'s U): the grid never exceeds the chunk count
   const int64_t CH = (int64_t)kEwThreads * (bf16 ? 2 * kMergeU : kMergeU);
@@ -442,6 +538,43 @@ extern "C" int hdp_merge_group_bf16dw(int n, const hdp_merge_item* items, void* 
     chunks += (ga.nv[ga.n] + CH - 1) / CH;
     bytes += 6.0 * it.n;
     if (++ga.n == kMergeGroupMax) {
+      const int rc = launch();
+      if (rc) return rc;
+    }
+  }
+  return launch();
+}
+
+extern "C" int hdp_copy_group(int n, const hdp_copy_item* items, void* stream) {
+  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "hdp_copy_group: bad item list");
+  for (int i = 0; i < n; ++i) {  // all of it before the first launch
+    HDP_CHECK_ARG(items[i].bytes >= 0, "hdp_copy_group: item %d has bytes < 0", i);
+    HDP_CHECK_ARG(items[i].bytes == 0 || (items[i].dst && items[i].src), "hdp_copy_group: item %d has a null pointer", i);
+  }
+  hipStream_t st = as_stream(stream);
+  CopyGroupArgs ga;
+  ga.n = 0;
+  double bytes = 0;
+  int64_t chunks = 0;
+  auto launch = [&]() -> int {
+    if (ga.n == 0) return HDP_OK;
+    const unsigned grid = (unsigned)(chunks < kMergeGrid ? chunks : kMergeGrid);
+    {
+      KTimer kt(K_COPY, st, 2.0 * bytes);
+      hipLaunchKernelGGL(copy_chunk_kernel, dim3(grid), dim3(kEwThreads), 0, st, ga);
+    }
+    HDP_CHECK_LAUNCH();
+    ga.n = 0;
+    bytes = 0;
+    chunks = 0;
+    return HDP_OK;
+  };
+  for (int i = 0; i < n; ++i) {
+    if (items[i].bytes == 0) continue;
+    ga.it[ga.n] = items[i];
+    chunks += copy_split(items[i].dst, items[i].src, items[i].bytes).nch;
+    bytes += (double)items[i].bytes;
+    if (++ga.n == kCopyGroupMax) {
       const int rc = launch();
       if (rc) return rc;
     }

@@ -41,6 +41,14 @@ class MergeItem(ctypes.Structure):
     _fields_ = [("W", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("n", ctypes.c_int64)]
 
 
+class CopyItem(ctypes.Structure):
+    """hdp_copy_item (include/hdpissa.h)."""
+    _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
+
+
+COPY_GROUP_MAX = 170  # non-empty items per launch of hdp_copy_group (its kernel-argument block)
+
+
 class SvdItem(ctypes.Structure):
     """hdp_svd_item (include/hdpissa.h)."""
     _fields_ = [("W", ctypes.c_void_p), ("out", ctypes.c_int64), ("in_", ctypes.c_int64), ("A_all", ctypes.c_void_p),
@@ -63,6 +71,7 @@ SIGNATURES = {
     "hdp_merge_group": (_c_int, [_c_int, ctypes.POINTER(MergeItem), _c_int, _c_vp]),
     "hdp_merge_group_bf16dw": (_c_int, [_c_int, ctypes.POINTER(MergeItem), _c_vp]),
     "hdp_fold_bf16": (_c_int, [_c_vp, _c_int, _c_i64, _c_vp, _c_i64, _c_vp]),
+    "hdp_copy_group": (_c_int, [_c_int, ctypes.POINTER(CopyItem), _c_vp]),
     "hdp_adam_factors": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
                                   _c_f, _c_f, _c_f, _c_int, _c_vp]),
     "hdp_delta_gemm": (_c_int, [_c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64,

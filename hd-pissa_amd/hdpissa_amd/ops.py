@@ -331,6 +331,21 @@ class HipOps:
             else:
                 check(lib().hdp_merge_group(len(run), arr, _dt(run[0][0]), _stream()), "hdp_merge_group")
 
+    def copy_group(self, pairs) -> None:
+        """dst <- src for many contiguous (dst, src) pairs of equal byte size (any dtypes) in one launch
+        per ``_lib.COPY_GROUP_MAX`` pairs: the shard exchange's pack and scatter (hdp_copy_group)."""
+        from ._lib import CopyItem
+        if not pairs:
+            return
+        arr = (CopyItem * len(pairs))()
+        for i, (dst, src) in enumerate(pairs):
+            _need_gpu(dst, src)
+            nb = dst.numel() * dst.element_size()
+            if nb != src.numel() * src.element_size() or not dst.is_contiguous() or not src.is_contiguous():
+                raise ValueError("copy_group: dst and src must be contiguous with equal byte sizes")
+            arr[i].dst, arr[i].src, arr[i].bytes = dst.data_ptr(), src.data_ptr(), nb
+        check(lib().hdp_copy_group(len(pairs), arr, _stream()), "hdp_copy_group")
+
     def fold_bf16(self, parts: torch.Tensor, out: torch.Tensor) -> None:
         """Rank-ordered bf16 fold (hp:389-392 rounding order): parts [nparts, n] float32 (rank i's
         term -bracket_i in row i), out [n] bfloat16 = bf16(...bf16(bf16(0 + p0) + p1)... + p_last)."""

@@ -7,7 +7,7 @@ merge -- ~48 N Wn bytes of HBM traffic per rank.  Here, per arena (a
   1. K3  one Adam launch over the flat arena: grad (x1e16) -> m, v -> delta; clears grad.
          (Wn = 1 with single-segment H2 plans -- bf16 W, r >= 32: Adam runs inside the plan's operand
          preparation instead, writing the delta halves of the fp16 panels as it goes)
-  2. exchange -- two interchangeable strategies (``exchange=``):
+  2. exchange -- three interchangeable strategies (``exchange=``):
      "gather"    (default) RCCL all-gather of the deltas only (A_i, B_i were shared at
                  init), bucketed on a side stream; per module ONE fused K4 launch with
                  K = 2 r Wn that recomputes sum_i (B'_i A'_i - B_i A_i) in the reference's
@@ -18,6 +18,14 @@ merge -- ~48 N Wn bytes of HBM traffic per rank.  Here, per arena (a
                  bf16 models: the same buckets exchanged rank-ordered (all-to-all of the float32
                  terms, bf16 fold in rank order, all-gather of the bf16 shards, K5), which is the
                  reference's per-rank bf16 rounding (hp:389-392) that a summing all-reduce loses.
+     "shard"     the gather exchange's delta all-gather, then rank k runs the K = 2 r Wn merge only on
+                 its own 1/Wn row block of every W (``shard_rows``: blocks in units of 8 rows, so row
+                 pointers stay 16-byte aligned) -- 1/Wn of gather's MFMA and panel work per rank -- and
+                 one all-gather per W bucket of the merged rows restores the replicated weight: the own
+                 rows packed into a send buffer and the other ranks' rows scattered into W_res by the
+                 grouped copy kernel (hdp_copy_group), the all-gather and scatter on the side stream under
+                 the next bucket's K4.  Every element of W is computed by one rank and copied to the
+                 others: the replicas are bitwise equal in both dtypes.  World size 1: the gather path.
   3. A.grad = B.grad = None  (hp:397-398).
 
 Semantics kept from the reference: Adam without weight decay, bias correction with the
@@ -50,6 +58,42 @@ def _buckets(sizes: List[int], cap: int) -> List[Tuple[int, int]]:
     return out
 
 
+def shard_rows(out: int, Wn: int, k: int) -> Tuple[int, int]:
+    """Rows [r0, r1) of an ``out``-row W that rank ``k`` of ``Wn`` merges under exchange="shard": equal
+    blocks of ``8 * ceil(out / (8 Wn))`` rows, so every block starts on a multiple of 8 rows (the W row and
+    the B / dB row then stay 16-byte aligned for any in and r); trailing ranks get a short block or none."""
+    block = 8 * -(-out // (8 * Wn))
+    return min(out, k * block), min(out, (k + 1) * block)
+
+
+def shard_item(item, Wn: int, k: int):
+    """Rank k's row block of one gathered K4 item ``(out, in, r, nseg, dA, dB, delta_stride, A, B,
+    factor_stride, dst)`` (dst the out x in W), or None if the rank owns no row of it.  A row block is an
+    item in its own right: out' = r1 - r0, dst = W[r0:r1], dB and B advanced by r0 * r floats (inside
+    every segment: the strides stay), dA and A as they are."""
+    out, inn, r, nseg, dA, dB, dstr, A, B, fstr, dst = item
+    r0, r1 = shard_rows(out, Wn, k)
+    if r1 <= r0:
+        return None
+    return (r1 - r0, inn, r, nseg, dA, dB[r0 * r:], dstr, A, B[r0 * r:], fstr, dst[r0:r1])
+
+
+class _ShardBucket:
+    """One W bucket of the shard exchange: modules [a, b) of one dtype; per module the byte offset of
+    its slot in a rank's shard (16-byte aligned, ``block * in`` elements long on every rank, whatever
+    rows the rank really owns) and the shard's length ``nbytes`` (equal on all ranks)."""
+
+    def __init__(self, layers, a: int, b: int, Wn: int):
+        self.a, self.b = a, b
+        self.slots, off = [], 0
+        for L in layers[a:b]:
+            self.slots.append(off)
+            block = shard_rows(L.out_features, Wn, 0)[1]
+            off += -(-block * L.in_features * L.W_res.element_size() // 16) * 16
+        self.nbytes = off
+        self.views = None  # (W_res pointers, dsts, pack, scatter), built on first use (_shard_views)
+
+
 class _ArenaPlan:
     def __init__(self, arena: FactorArena, exchange: str, bucket_bytes: int):
         self.arena = arena
@@ -60,9 +104,28 @@ class _ArenaPlan:
         ends = [arena.offsets[i + 1][0] if i + 1 < n else F for i in range(n)]
         starts = [arena.offsets[i][0] for i in range(n)]
         self.g_buckets = []
-        for a, b in _buckets([ends[i] - starts[i] for i in range(n)], max(1, bucket_bytes // 4 // max(Wn, 1))):
+        # (shard: bucket_bytes bounds the W buckets; the delta buckets keep gather's default bound)
+        g_bytes = min(bucket_bytes, 256 << 20) if exchange == "shard" else bucket_bytes
+        for a, b in _buckets([ends[i] - starts[i] for i in range(n)], max(1, g_bytes // 4 // max(Wn, 1))):
             self.g_buckets.append((a, b, starts[a], ends[b - 1]))
-        self.delta_all = torch.empty(Wn * F, dtype=torch.float32, device=dev) if (exchange == "gather" and Wn > 1) else None
+        self.delta_all = torch.empty(Wn * F, dtype=torch.float32, device=dev) \
+            if (exchange in ("gather", "shard") and Wn > 1) else None
+        # shard: W buckets over dense W bytes, split where the dtype changes; two send and two gather
+        # buffers (bytes) sized for the longest shard
+        self.s_buckets: List[_ShardBucket] = []
+        self.s_send: List[torch.Tensor] = []
+        self.s_gath: List[torch.Tensor] = []
+        if exchange == "shard" and Wn > 1:
+            run = 0
+            for i in range(1, n + 1):
+                if i == n or arena.layers[i].W_res.dtype != arena.layers[run].W_res.dtype:
+                    sizes = [L.W_res.numel() * L.W_res.element_size() for L in arena.layers[run:i]]
+                    self.s_buckets += [_ShardBucket(arena.layers, run + a, run + b, Wn)
+                                       for a, b in _buckets(sizes, max(1, bucket_bytes))]
+                    run = i
+            cap = max(sb.nbytes for sb in self.s_buckets)
+            self.s_send = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.s_gath = [torch.empty(Wn * cap, dtype=torch.uint8, device=dev) for _ in range(2)]
         # allreduce: buckets over dense dW sizes
         self.a_buckets = []
         self.dw_bufs: List[torch.Tensor] = []
@@ -126,8 +189,8 @@ class HDPissaStep:
     def __init__(self, model: nn.Module, world_size: int, rank: int = 0, comm=None, ops=None,
                  exchange: str = "gather", bucket_bytes: Optional[int] = None, beta1: float = 0.9,
                  beta2: float = 0.999, eps: float = 1e-8):
-        if exchange not in ("gather", "allreduce"):
-            raise ValueError("exchange must be 'gather' or 'allreduce'")
+        if exchange not in ("gather", "allreduce", "shard"):
+            raise ValueError("exchange must be 'gather', 'allreduce' or 'shard'")
         self.layers = [m for _, m in custom_layers(model)]
         if not self.layers:
             raise ValueError("model has no CustomLinearLayer")
@@ -136,7 +199,8 @@ class HDPissaStep:
         self.beta1, self.beta2, self.eps = beta1, beta2, eps
         if bucket_bytes is None:
             # gather: ~256 MB of per-rank deltas per all-gather bucket; allreduce: 1 GB of dense
-            # float32 dW per bucket (two buffers): bigger K4-store / K5 launches, fewer collectives
+            # float32 dW per bucket (two buffers): bigger K4-store / K5 launches, fewer collectives;
+            # shard: 1 GB of W per bucket (the delta all-gather keeps gather's 256 MB)
             bucket_bytes = (256 << 20) if exchange == "gather" else (1 << 30)
         arenas: Dict[int, FactorArena] = {}
         for L in self.layers:
@@ -229,15 +293,17 @@ class HDPissaStep:
                            zero_grad=True)
             return
         ops.adam(arena.grad, arena.m, arena.v, arena.delta, t, lr, self.beta1, self.beta2, self.eps, zero_grad=True)
-        if self.exchange == "gather":
+        if self.exchange == "gather" or (self.exchange == "shard" and Wn == 1):
             self._gather(plan)
+        elif self.exchange == "shard":
+            self._shard(plan)
         else:
             self._allreduce(plan)
 
     def _fused_plans(self, plan: _ArenaPlan, lr: float, t: int):
         """The Wn = 1 gather plans when every one of them folds Adam in (single-segment H2 merges:
         bf16 W at r >= 32), else None (HDP_FUSED_ADAM=0 turns the fold off)."""
-        if not (self.exchange == "gather" and self.world_size == 1 and self.grouped) or not self._fuse_adam:
+        if not (self.exchange in ("gather", "shard") and self.world_size == 1 and self.grouped) or not self._fuse_adam:
             return None
         from .ops import adam_delta_bound
         if adam_delta_bound(t, lr, self.beta1, self.beta2) is None:
@@ -271,20 +337,7 @@ class HDPissaStep:
                 ops.delta_gemm(*it, HDP_DW_MERGE, it[-1].dtype == torch.bfloat16)
             return
         cur = torch.cuda.current_stream(self.device) if self.on_gpu else None
-        events = []
-        if self.on_gpu:
-            ready = torch.cuda.Event()
-            ready.record(cur)
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ready)
-                for (a, b, s, e) in plan.g_buckets:
-                    self.comm.allgather(arena.delta[s:e], plan.delta_all[Wn * s:Wn * e])
-                    ev = torch.cuda.Event()
-                    ev.record(self.side)
-                    events.append(ev)
-        else:
-            for (a, b, s, e) in plan.g_buckets:
-                self.comm.allgather(arena.delta[s:e], plan.delta_all[Wn * s:Wn * e])
+        events = self._gather_deltas(plan, cur)
         for bi, (a, b, s, e) in enumerate(plan.g_buckets):
             if self.on_gpu:
                 cur.wait_event(events[bi])
@@ -306,6 +359,124 @@ class HDPissaStep:
                 continue
             for it in items():
                 ops.delta_gemm(*it, HDP_DW_MERGE, it[-1].dtype == torch.bfloat16)
+
+    def _gather_deltas(self, plan: _ArenaPlan, cur) -> list:
+        """The bucketed all-gather of the deltas into ``delta_all`` (on the side stream on the GPU);
+        returns one event per delta bucket (none on the CPU, where the collectives are synchronous)."""
+        arena, Wn = plan.arena, self.world_size
+        events = []
+        if self.on_gpu:
+            ready = torch.cuda.Event()
+            ready.record(cur)
+            with torch.cuda.stream(self.side):
+                self.side.wait_event(ready)
+                for (a, b, s, e) in plan.g_buckets:
+                    self.comm.allgather(arena.delta[s:e], plan.delta_all[Wn * s:Wn * e])
+                    ev = torch.cuda.Event()
+                    ev.record(self.side)
+                    events.append(ev)
+        else:
+            for (a, b, s, e) in plan.g_buckets:
+                self.comm.allgather(arena.delta[s:e], plan.delta_all[Wn * s:Wn * e])
+        return events
+
+    # -- exchange = "shard" --------------------------------------------------------------
+    def _shard_items(self, plan: _ArenaPlan, sb: _ShardBucket, k: int) -> list:
+        """Rank k's K4 items of one W bucket: its row block (``shard_item``) of every module that gives
+        it rows, on the gathered deltas and factors as the gather exchange lays them out."""
+        arena, Wn, F = plan.arena, self.world_size, plan.arena.F
+        fac = arena.fac_all.view(-1)
+        items = []
+        gi = 0
+        for i in range(sb.a, sb.b):
+            while plan.g_buckets[gi][1] <= i:
+                gi += 1
+            _, _, s, e = plan.g_buckets[gi]  # the delta bucket that holds module i
+            base = plan.delta_all[Wn * s:]
+            L = arena.layers[i]
+            oa, ob = arena.offsets[i]
+            it = shard_item((L.out_features, L.in_features, L.r, Wn, base[oa - s:], base[ob - s:], e - s,
+                             fac[oa:], fac[ob:], F, L.W_res), Wn, k)
+            if it is not None:
+                items.append(it)
+        return items
+
+    def _shard_views(self, plan: _ArenaPlan, sb: _ShardBucket):
+        """(dsts, pack, scatter) of one W bucket, cached while no W_res moved: this rank's row blocks
+        (the K4 destinations), and per buffer pair the (dst, src) byte ranges that move them into the send
+        buffer and every other rank's rows from the gather buffer into W_res."""
+        layers, Wn = plan.arena.layers[sb.a:sb.b], self.world_size
+        ptrs = tuple(L.W_res.data_ptr() for L in layers)
+        if sb.views is not None and sb.views[0] == ptrs:
+            return sb.views[1:]
+        dsts, pack, scat = [], ([], []), ([], [])
+        for L, off in zip(layers, sb.slots):
+            row = L.in_features * L.W_res.element_size()
+            for j in range(Wn):
+                r0, r1 = shard_rows(L.out_features, Wn, j)
+                if r1 <= r0:
+                    continue
+                rows = L.W_res[r0:r1].reshape(-1).view(torch.uint8)
+                if j == self.rank:
+                    dsts.append(L.W_res[r0:r1])
+                for q in range(2):
+                    if j == self.rank:
+                        pack[q].append((plan.s_send[q][off:off + (r1 - r0) * row], rows))
+                    else:
+                        o = j * sb.nbytes + off
+                        scat[q].append((rows, plan.s_gath[q][o:o + (r1 - r0) * row]))
+        sb.views = (ptrs, dsts, pack, scat)
+        return dsts, pack, scat
+
+    def _copy(self, pairs) -> None:
+        if hasattr(self.ops, "copy_group"):  # the pack / scatter as one launch
+            self.ops.copy_group(pairs)
+        else:
+            for dst, src in pairs:
+                dst.copy_(src)
+
+    def _shard(self, plan: _ArenaPlan) -> None:
+        ops, Wn = self.ops, self.world_size
+        cur = torch.cuda.current_stream(self.device) if self.on_gpu else None
+        events = self._gather_deltas(plan, cur)
+        freed = [None, None]
+        last = None
+        gi = 0
+        for bi, sb in enumerate(plan.s_buckets):
+            q = bi % 2
+            while plan.g_buckets[gi][1] < sb.b:
+                gi += 1
+            if self.on_gpu:
+                cur.wait_event(events[gi])  # the delta buckets that cover modules [a, b) (in stream order)
+            dsts, pack, scat = self._shard_views(plan, sb)
+            if dsts and self.grouped:  # (no rows in the whole bucket: no plan)
+                for p, _ in plan.delta_plans(("s", bi), ops, lambda sb=sb: self._shard_items(plan, sb, self.rank),
+                                             HDP_DW_MERGE, dsts):
+                    p.run()
+            elif dsts:
+                for it in self._shard_items(plan, sb, self.rank):
+                    ops.delta_gemm(*it, HDP_DW_MERGE, it[-1].dtype == torch.bfloat16)
+            send, gath = plan.s_send[q][:sb.nbytes], plan.s_gath[q][:Wn * sb.nbytes]
+            if not self.on_gpu:
+                self._copy(pack[q])
+                self.comm.allgather_any(send, gath)
+                self._copy(scat[q])
+                continue
+            if freed[q] is not None:
+                cur.wait_event(freed[q])  # the all-gather and scatter that read this buffer pair are done
+            self._copy(pack[q])
+            computed = torch.cuda.Event()
+            computed.record(cur)
+            with torch.cuda.stream(self.side):
+                self.side.wait_event(computed)
+                self.comm.allgather_any(send, gath)
+                self._copy(scat[q])  # (the own block is already in place)
+                ev = torch.cuda.Event()
+                ev.record(self.side)
+            freed[q] = ev
+            last = ev
+        if self.on_gpu and last is not None:
+            cur.wait_event(last)
 
     # -- exchange = "allreduce" ----------------------------------------------------------
     def _allreduce(self, plan: _ArenaPlan) -> None:

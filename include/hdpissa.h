@@ -85,6 +85,25 @@ int hdp_merge_group_bf16dw(int n, const hdp_merge_item* items, void* stream);
  * out: n bf16 values. */
 int hdp_fold_bf16(const float* parts, int nparts, int64_t stride, void* out, int64_t n, void* stream);
 
+/* Grouped contiguous copy -- the device side of the sharded merge exchange (exchange="shard"; the
+ * reference has no counterpart: every rank there recomputes the whole of hp:389-394).  Each rank merges
+ * only its own row block of every W; a row block of a row-major matrix is one byte range, so packing the
+ * own blocks into the all-gather's send buffer and scattering the other ranks' blocks from its receive
+ * buffer into W are both lists of ranges, copied here in one launch per 170 non-empty items (what fits
+ * the kernel-argument block) instead of one copy per range.
+ *   dst[0 .. bytes) <- src[0 .. bytes)   for every item; bytes == 0 items are skipped.
+ * Any byte count and any alignment: an item whose dst and src share their offset within 16 bytes moves
+ * as 16-byte vectors between a byte-wise head and tail, any other item byte by byte; nothing outside
+ * [ptr, ptr + bytes) is read or written.  Ranges of one call must not overlap each other's dst (not
+ * checked).  items is a HOST array read during the call; bytes < 0 or a null pointer with bytes > 0 is
+ * HDP_EINVAL before anything is launched. */
+typedef struct {
+  void* dst;
+  const void* src;
+  int64_t bytes;
+} hdp_copy_item;
+int hdp_copy_group(int n, const hdp_copy_item* items, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * K3 Adam-on-factors -- replaces hp:356-373 for a flat arena of n float32 factor entries
  * (all modules' A-side and B-side concatenated).  Per element:
