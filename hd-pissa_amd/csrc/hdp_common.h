@@ -50,7 +50,8 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 // ---- live per-kernel timing (hdp_timing_*): HIP events bracket each launch on its stream --
 enum KernelId {
   K_MERGE = 0, K_ADAM, K_DELTA, K_DELTA_MULTI, K_PROBE_P1, K_PROBE_P2, K_PROBE_FINISH, K_PROBE_REDUCE, K_SWEEP_A, K_SWEEP_B, K_SWEEP_C,
-  K_SVD_GEMM, K_DELTA_PACK, K_FOLD, K_PROBE_DROPOUT, K_PROBE_DROPOUT_FINISH, K_COPY, K_COUNT
+  K_SVD_GEMM, K_DELTA_PACK, K_FOLD, K_PROBE_DROPOUT, K_PROBE_DROPOUT_FINISH, K_COPY, K_SUMSQ, K_CLIP_FINISH,
+  K_COUNT
 };
 bool timing_on();
 void timing_record(int kid, hipEvent_t a, hipEvent_t b, double bytes, double flops);
@@ -190,10 +191,10 @@ struct AdamScalars {
   float grad_scale, b1, omb1, b2, omb2, bc1, bc2, lr, eps;
 };
 
-__device__ __forceinline__ void adam1(float& g, float& m, float& v, float& d, const AdamScalars& s) {
+// the update from the scaled gradient gs on (adam1 and adam1_clip below)
+__device__ __forceinline__ void adam_gs(const float gs, float& m, float& v, float& d, const AdamScalars& s) {
 #pragma clang fp contract(off)
   // plain operators in this contract(off) scope: every product/sum rounds on its own
-  const float gs = g * s.grad_scale;
   const float b1m = s.b1 * m, og = s.omb1 * gs;
   m = b1m + og;
   const float g2 = gs * gs;
@@ -205,11 +206,36 @@ __device__ __forceinline__ void adam1(float& g, float& m, float& v, float& d, co
   d = num / (sqrtf(vh) + s.eps);
 }
 
+__device__ __forceinline__ void adam1(float& g, float& m, float& v, float& d, const AdamScalars& s) {
+#pragma clang fp contract(off)
+  const float gs = g * s.grad_scale;
+  adam_gs(gs, m, v, d, s);
+}
+
+// under a clip record (hdp_clip_state): Adam on gs * coef, the clip its own float32 multiply in front of
+// the sequence (gs * 1.0f is exact: an unclipped step keeps adam1's bits)
+__device__ __forceinline__ void adam1_clip(float& g, float& m, float& v, float& d, const AdamScalars& s,
+                                           const float coef) {
+#pragma clang fp contract(off)
+  const float gs = g * s.grad_scale;
+  const float gc = gs * coef;
+  adam_gs(gc, m, v, d, s);
+}
+
 // The probe's hand-off error word: while it is set the update is refused on the device
 // (m and v stay as they were, delta = 0, so the merge that follows adds exactly 0 to W_res)
 __device__ __forceinline__ bool adam_refused(const int* err) {
   return __builtin_amdgcn_readfirstlane(
              err != nullptr && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ? 1 : 0) != 0;
+}
+
+// The clip record (hdp_clip_state, written by clip_finish_kernel earlier on the stream), read once per
+// workgroup like the error word: its skip flag joins the refusal, its coefficient scales the gradient
+__device__ __forceinline__ bool clip_read(const hdp_clip_state* clip, float& coef) {
+  const int skip = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&clip->skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  coef = __uint_as_float(__builtin_amdgcn_readfirstlane(
+      __hip_atomic_load(reinterpret_cast<const unsigned*>(&clip->coef), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+  return skip != 0;
 }
 
 }  // namespace hdp

@@ -1765,6 +1765,7 @@ struct AdamPackArgs {
   float* m;
   float* v;
   const int* err;      // probe error word (refusal: delta = 0, m / v untouched)
+  const hdp_clip_state* clip;  // clip record of the step (CLIP kernels; else null and never read)
   AdamScalars s;
   int zero;            // clear grad
 };
@@ -1857,6 +1858,9 @@ static inline int64_t h2_ap_threads(int64_t out, int64_t in, int r) {
   return out * qr + (in + 3) / 4 * qr;
 }
 
+// CLIP: under a clip record (hdp_clip_state) -- its skip flag joins the refusal and its coefficient scales
+// the gradient (adam1_clip); without one the kernel is the instruction sequence it always was
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k4_h2_adam_pack_kernel(const DeltaArgs* __restrict__ items,
                                                               const int64_t* __restrict__ ap_start, int n,
                                                               AdamPackArgs ap) {
@@ -1869,7 +1873,15 @@ __global__ __launch_bounds__(256) void k4_h2_adam_pack_kernel(const DeltaArgs* _
     if (ap_start[mid] <= e0) lo = mid;
     else hi = mid - 1;
   }
-  const bool refused = adam_refused(ap.err);
+  bool refused_ = adam_refused(ap.err);
+  float coef_ = 1.f;
+  if constexpr (CLIP) refused_ |= clip_read(ap.clip, coef_);
+  const bool refused = refused_;
+  const float coef = coef_;
+  auto adam_e = [&](float& gq, float& mq, float& vq, float& dq) {
+    if constexpr (CLIP) adam1_clip(gq, mq, vq, dq, ap.s, coef);
+    else adam1(gq, mq, vq, dq, ap.s);
+  };
   const DeltaArgs& a = items[lo];
   const int r = a.r, K = 2 * r;
   const bool w8 = r % 8 == 0;  // item-uniform: 8 k-slots per thread (h2_ap_threads)
@@ -1895,7 +1907,7 @@ __global__ __launch_bounds__(256) void k4_h2_adam_pack_kernel(const DeltaArgs* _
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float gq = gg[q], mq = mm[q], vq = vv[q], dq;
-          adam1(gq, mq, vq, dq, ap.s);
+          adam_e(gq, mq, vq, dq);
           mm[q] = mq;
           vv[q] = vq;
           dd[q] = dq;
@@ -1916,7 +1928,7 @@ __global__ __launch_bounds__(256) void k4_h2_adam_pack_kernel(const DeltaArgs* _
         *gptr(dq_p) = 0.f;
       } else {
         float gq = *gptr(ap.g + o2), mq = *gptr(ap.m + o2), vq = *gptr(ap.v + o2), dq;
-        adam1(gq, mq, vq, dq, ap.s);
+        adam_e(gq, mq, vq, dq);
         *gptr(ap.m + o2) = mq;
         *gptr(ap.v + o2) = vq;
         *gptr(dq_p) = dq;
@@ -1974,7 +1986,7 @@ __global__ __launch_bounds__(256) void k4_h2_adam_pack_kernel(const DeltaArgs* _
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float gq = G[j][q], mq = M[j][q], vq = V[j][q], dq;
-        adam1(gq, mq, vq, dq, ap.s);
+        adam_e(gq, mq, vq, dq);
         M[j][q] = mq;
         V[j][q] = vq;
         dd[j][q] = dq;
@@ -3019,10 +3031,10 @@ extern "C" int hdp_delta_plan_invalidate(hdp_delta_plan p) {
   return HDP_OK;
 }
 
-extern "C" int hdp_delta_plan_run_adam(hdp_delta_plan p, float* grad, float* m, float* v, float* delta,
-                                       float grad_scale, float beta1, float one_minus_beta1, float beta2,
-                                       float one_minus_beta2, float bc1, float bc2, float lr, float eps,
-                                       float delta_bound, int zero_grad, void* stream) {
+static int plan_run_adam(hdp_delta_plan p, float* grad, float* m, float* v, float* delta, float grad_scale,
+                         float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float bc1,
+                         float bc2, float lr, float eps, float delta_bound, int zero_grad,
+                         const hdp_clip_state* clip, void* stream) {
   HDP_CHECK_ARG(p && p->d_items && p->grid > 0, "hdp_delta_plan_run_adam: invalid plan");
   HDP_CHECK_ARG(p->fused, "hdp_delta_plan_run_adam: the plan has no fused Adam (single-segment H2 merge plans only)");
   HDP_CHECK_ARG(grad && m && v && delta, "hdp_delta_plan_run_adam: null arena pointer");
@@ -3054,10 +3066,15 @@ extern "C" int hdp_delta_plan_run_adam(hdp_delta_plan p, float* grad, float* m, 
     ap.m = m;
     ap.v = v;
     ap.err = probe_err_device();
+    ap.clip = clip;
     ap.s = AdamScalars{grad_scale, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, bc2, lr, eps};
     ap.zero = zero_grad ? 1 : 0;
-    hipLaunchKernelGGL(k4_h2_adam_pack_kernel, dim3((unsigned)(p->ap_total / 256)), dim3(256), 0, st, p->d_items,
-                       p->d_ap_start, p->n, ap);
+    if (clip)
+      hipLaunchKernelGGL(k4_h2_adam_pack_kernel<true>, dim3((unsigned)(p->ap_total / 256)), dim3(256), 0, st,
+                         p->d_items, p->d_ap_start, p->n, ap);
+    else
+      hipLaunchKernelGGL(k4_h2_adam_pack_kernel<false>, dim3((unsigned)(p->ap_total / 256)), dim3(256), 0, st,
+                         p->d_items, p->d_ap_start, p->n, ap);
   }
   HDP_CHECK_LAUNCH();
   {  // fallback: only if a delta exceeded D (moments not from this Adam sequence) -- then the gated
@@ -3071,6 +3088,23 @@ extern "C" int hdp_delta_plan_run_adam(hdp_delta_plan p, float* grad, float* m, 
   }
   HDP_CHECK_LAUNCH();
   return plan_launch(p, st, false);
+}
+
+extern "C" int hdp_delta_plan_run_adam(hdp_delta_plan p, float* grad, float* m, float* v, float* delta,
+                                       float grad_scale, float beta1, float one_minus_beta1, float beta2,
+                                       float one_minus_beta2, float bc1, float bc2, float lr, float eps,
+                                       float delta_bound, int zero_grad, void* stream) {
+  return plan_run_adam(p, grad, m, v, delta, grad_scale, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, bc2,
+                       lr, eps, delta_bound, zero_grad, nullptr, stream);
+}
+
+extern "C" int hdp_delta_plan_run_adam_clip(hdp_delta_plan p, float* grad, float* m, float* v, float* delta,
+                                            float grad_scale, float beta1, float one_minus_beta1, float beta2,
+                                            float one_minus_beta2, float bc1, float bc2, float lr, float eps,
+                                            float delta_bound, int zero_grad, const hdp_clip_state* clip,
+                                            void* stream) {
+  return plan_run_adam(p, grad, m, v, delta, grad_scale, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, bc2,
+                       lr, eps, delta_bound, zero_grad, clip, stream);
 }
 
 extern "C" int hdp_delta_plan_fused_fallback(hdp_delta_plan p, int* taken) {

@@ -315,12 +315,17 @@ __global__ void merge_scalar_kernel(void* W, int dt, const float* dW, int64_t be
 // contiguous chunks of kAdamU x 256 vectors per workgroup step (the merge's form: every load of the
 // chunk issued before its stores)
 constexpr int kAdamU = 2;
-template <bool ZERO>
+// CLIP: under a clip record (hdp_clip_state) -- its skip flag joins the refusal and its coefficient
+// scales the gradient (adam1_clip); without one the kernel is the instruction sequence it always was
+template <bool ZERO, bool CLIP>
 __global__ __launch_bounds__(kEwThreads) void adam_kernel(float* __restrict__ grad, float* __restrict__ m,
                                                           float* __restrict__ v, float* __restrict__ delta,
-                                                          int64_t n4, AdamScalars s, const int* err) {
+                                                          int64_t n4, AdamScalars s, const int* err,
+                                                          const hdp_clip_state* clip) {
   constexpr int64_t CH = (int64_t)kEwThreads * kAdamU;
-  const bool refused = adam_refused(err);
+  bool refused = adam_refused(err);
+  float coef = 1.f;
+  if constexpr (CLIP) refused |= clip_read(clip, coef);
   HDP_GLOBAL f32x4* G = reinterpret_cast<HDP_GLOBAL f32x4*>(gptr(grad));
   HDP_GLOBAL f32x4* M = reinterpret_cast<HDP_GLOBAL f32x4*>(gptr(m));
   HDP_GLOBAL f32x4* V = reinterpret_cast<HDP_GLOBAL f32x4*>(gptr(v));
@@ -349,7 +354,8 @@ __global__ __launch_bounds__(kEwThreads) void adam_kernel(float* __restrict__ gr
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float gq = g[u][q], mq = mm[u][q], vq = vv[u][q], dq;
-        adam1(gq, mq, vq, dq, s);
+        if constexpr (CLIP) adam1_clip(gq, mq, vq, dq, s, coef);
+        else adam1(gq, mq, vq, dq, s);
         mm[u][q] = mq;
         vv[u][q] = vq;
         dd[q] = dq;
@@ -362,9 +368,13 @@ __global__ __launch_bounds__(kEwThreads) void adam_kernel(float* __restrict__ gr
   }
 }
 
+template <bool CLIP>
 __global__ void adam_scalar_kernel(float* grad, float* m, float* v, float* delta, int64_t begin,
-                                   int64_t n, AdamScalars s, int zero, const int* err) {
-  const bool refused = adam_refused(err);
+                                   int64_t n, AdamScalars s, int zero, const int* err,
+                                   const hdp_clip_state* clip) {
+  bool refused = adam_refused(err);
+  float coef = 1.f;
+  if constexpr (CLIP) refused |= clip_read(clip, coef);
   for (int64_t i = begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     if (refused) {
@@ -373,12 +383,121 @@ __global__ void adam_scalar_kernel(float* grad, float* m, float* v, float* delta
       continue;
     }
     float g = grad[i], mq = m[i], vq = v[i], d;
-    adam1(g, mq, vq, d, s);
+    if constexpr (CLIP) adam1_clip(g, mq, vq, d, s, coef);
+    else adam1(g, mq, vq, d, s);
     m[i] = mq;
     v[i] = vq;
     delta[i] = d;
     if (zero) grad[i] = 0.f;
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// Global gradient norm (hdp_grad_sumsq / hdp_clip_finish): sum of double(float32(g * grad_scale))^2 over
+// an arena.  A streaming read in K3's form -- a workgroup owns kSumsqU x 256 consecutive 16-byte vectors
+// at a time, every load of the chunk issued before its first use, non-temporal (each byte is read once
+// here; K3 reads it again, from HBM either way at arena sizes) -- with one float64 accumulator per lane.
+// The lanes are reduced in a fixed order (xor butterfly over the wave, then the 4 waves through LDS in
+// wave order) and every workgroup writes ONE partial to its own workspace slot: no atomics, the same
+// bits on every run.  A float32 square would underflow for raw gradients and overflow for gs ~ 1e25;
+// the float64 square of a float32 does neither.
+// ---------------------------------------------------------------------------------------
+constexpr int kSumsqU = 2;               // vectors per lane per chunk (K3's)
+constexpr int kSumsqScalarBlocks = 64;   // scalar kernel (unaligned base / n % 4 tail): slots of its own
+
+__device__ __forceinline__ double sumsq_block_reduce(double acc, double* red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(kEwThreads) void grad_sumsq_kernel(const float* __restrict__ grad, int64_t n4,
+                                                                float grad_scale, double* __restrict__ part) {
+#pragma clang fp contract(off)
+  constexpr int64_t CH = (int64_t)kEwThreads * kSumsqU;
+  __shared__ double red[kEwThreads / 64];
+  const HDP_GLOBAL f32x4* G = reinterpret_cast<const HDP_GLOBAL f32x4*>(gptr(grad));
+  double acc = 0.0;
+  for (int64_t c = (int64_t)blockIdx.x * CH; c < n4; c += (int64_t)gridDim.x * CH) {
+    f32x4 g[kSumsqU];
+#pragma unroll
+    for (int u = 0; u < kSumsqU; ++u) {
+      const int64_t i = c + u * kEwThreads + threadIdx.x;
+      g[u] = i < n4 ? __builtin_nontemporal_load(G + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int u = 0; u < kSumsqU; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const double gs = (double)(g[u][q] * grad_scale);  // the float32 product K3 forms, then widened
+        acc += gs * gs;
+      }
+  }
+  const double tot = sumsq_block_reduce(acc, red);
+  if (threadIdx.x == 0) *gptr(part + blockIdx.x) = tot;
+}
+
+__global__ __launch_bounds__(kEwThreads) void grad_sumsq_scalar_kernel(const float* __restrict__ grad, int64_t begin,
+                                                                       int64_t n, float grad_scale,
+                                                                       double* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ double red[kEwThreads / 64];
+  double acc = 0.0;
+  for (int64_t i = begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const double gs = (double)(grad[i] * grad_scale);
+    acc += gs * gs;
+  }
+  const double tot = sumsq_block_reduce(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+// vals[0] + vals[1] + ... in index order, one workgroup of kEwThreads; the result is thread 0's.  The
+// workgroup stages kSumTile values at a time in LDS with coalesced loads and thread 0 adds them from there:
+// a serial loop over global memory pays one HBM round trip per value (2048 partials: ~0.1 ms, more than the
+// streaming kernel takes over a 40 M arena)
+constexpr int kSumTile = 2048;
+__device__ __forceinline__ double ordered_sum(const double* __restrict__ vals, int n, double* lds) {
+#pragma clang fp contract(off)
+  double s = 0.0;
+  for (int base = 0; base < n; base += kSumTile) {  // (workgroup-uniform)
+    const int cnt = n - base < kSumTile ? n - base : kSumTile;
+    for (int i = threadIdx.x; i < cnt; i += kEwThreads) lds[i] = vals[base + i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll 8
+      for (int i = 0; i < cnt; ++i) s += lds[i];
+    }
+    __syncthreads();
+  }
+  return s;
+}
+
+// out[0] = vals[0] + vals[1] + ... in index order (the per-workgroup partials: at most 2048 + 64)
+__global__ __launch_bounds__(kEwThreads) void sum_f64_kernel(const double* __restrict__ vals, int n,
+                                                             double* __restrict__ out) {
+  __shared__ double lds[kSumTile];
+  const double s = ordered_sum(vals, n, lds);
+  if (threadIdx.x == 0) *out = s;
+}
+
+// the clip record from the per-arena / per-rank sums, added in index order (one workgroup)
+__global__ __launch_bounds__(kEwThreads) void clip_finish_kernel(const double* __restrict__ sums, int n,
+                                                                 float max_norm, hdp_clip_state* st) {
+#pragma clang fp contract(off)
+  __shared__ double lds[kSumTile];
+  const double s = ordered_sum(sums, n, lds);
+  if (threadIdx.x != 0) return;
+  const bool skip = !(fabs(s) <= 1.7976931348623157e308);  // inf or NaN
+  const float norm = (float)sqrt(s);                           // IEEE sqrt, then one rounding to float32
+  const float q = max_norm / (norm + 1e-6f);                   // IEEE float32 division
+  st->sumsq = s;
+  st->norm = norm;
+  st->coef = skip ? 1.f : (q < 1.0f ? q : 1.0f);
+  st->skip = skip ? 1 : 0;
+  st->skipped_total += skip ? 1 : 0;
 }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -457,15 +576,12 @@ extern "C" int hdp_merge_group(int n, const hdp_merge_item* items, int w_dtype, 
   return launch();
 }
 
-extern "C" int hdp_adam_factors(float* grad, float* m, float* v, float* delta, int64_t n,
-                                float grad_scale, float beta1, float one_minus_beta1, float beta2,
-                                float one_minus_beta2, float bc1, float bc2, float lr, float eps,
-                                int zero_grad, void* stream) {
-  HDP_CHECK_ARG(n >= 0, "hdp_adam_factors: n < 0");
+static int adam_factors_impl(const char* who, float* grad, float* m, float* v, float* delta, int64_t n,
+                             const AdamScalars& s, int zero_grad, const hdp_clip_state* clip, void* stream) {
+  HDP_CHECK_ARG(n >= 0, "%s: n < 0", who);
   if (n == 0) return HDP_OK;
-  HDP_CHECK_ARG(grad && m && v && delta, "hdp_adam_factors: null pointer");
-  HDP_CHECK_ARG(bc1 != 0.f && bc2 != 0.f, "hdp_adam_factors: bias correction is zero (t == 0?)");
-  AdamScalars s{grad_scale, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, bc2, lr, eps};
+  HDP_CHECK_ARG(grad && m && v && delta, "%s: null pointer", who);
+  HDP_CHECK_ARG(s.bc1 != 0.f && s.bc2 != 0.f, "%s: bias correction is zero (t == 0?)", who);
   hipStream_t st = as_stream(stream);
   const int* err = probe_err_device();
   int64_t done = 0;
@@ -474,10 +590,16 @@ extern "C" int hdp_adam_factors(float* grad, float* m, float* v, float* delta, i
     if (n4) {
       KTimer kt(K_ADAM, st, 28.0 * 4 * n4);
       const dim3 grid(ew_grid(n4, kAdamU));
-      if (zero_grad)
-        hipLaunchKernelGGL(adam_kernel<true>, grid, dim3(kEwThreads), 0, st, grad, m, v, delta, n4, s, err);
-      else
-        hipLaunchKernelGGL(adam_kernel<false>, grid, dim3(kEwThreads), 0, st, grad, m, v, delta, n4, s, err);
+#define HDP_ADAM_LAUNCH(Z, C) \
+  hipLaunchKernelGGL((adam_kernel<Z, C>), grid, dim3(kEwThreads), 0, st, grad, m, v, delta, n4, s, err, clip)
+      if (clip) {
+        if (zero_grad) HDP_ADAM_LAUNCH(true, true);
+        else HDP_ADAM_LAUNCH(false, true);
+      } else {
+        if (zero_grad) HDP_ADAM_LAUNCH(true, false);
+        else HDP_ADAM_LAUNCH(false, false);
+      }
+#undef HDP_ADAM_LAUNCH
       HDP_CHECK_LAUNCH();
     }
     done = n4 * 4;
@@ -488,11 +610,107 @@ extern "C" int hdp_adam_factors(float* grad, float* m, float* v, float* delta, i
     if (blocks > 2048) blocks = 2048;
     {
       KTimer kt(K_ADAM, st, 28.0 * rest);
-      hipLaunchKernelGGL(adam_scalar_kernel, dim3(blocks), dim3(256), 0, st, grad, m, v, delta, done, n, s,
-                         zero_grad, err);
+      if (clip)
+        hipLaunchKernelGGL(adam_scalar_kernel<true>, dim3(blocks), dim3(256), 0, st, grad, m, v, delta, done, n, s,
+                           zero_grad, err, clip);
+      else
+        hipLaunchKernelGGL(adam_scalar_kernel<false>, dim3(blocks), dim3(256), 0, st, grad, m, v, delta, done, n, s,
+                           zero_grad, err, clip);
     }
     HDP_CHECK_LAUNCH();
   }
+  return HDP_OK;
+}
+
+extern "C" int hdp_adam_factors(float* grad, float* m, float* v, float* delta, int64_t n,
+                                float grad_scale, float beta1, float one_minus_beta1, float beta2,
+                                float one_minus_beta2, float bc1, float bc2, float lr, float eps,
+                                int zero_grad, void* stream) {
+  const AdamScalars s{grad_scale, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, bc2, lr, eps};
+  return adam_factors_impl("hdp_adam_factors", grad, m, v, delta, n, s, zero_grad, nullptr, stream);
+}
+
+extern "C" int hdp_adam_factors_clip(float* grad, float* m, float* v, float* delta, int64_t n,
+                                     float grad_scale, float beta1, float one_minus_beta1, float beta2,
+                                     float one_minus_beta2, float bc1, float bc2, float lr, float eps,
+                                     int zero_grad, const hdp_clip_state* clip, void* stream) {
+  const AdamScalars s{grad_scale, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, bc2, lr, eps};
+  return adam_factors_impl("hdp_adam_factors_clip", grad, m, v, delta, n, s, zero_grad, clip, stream);
+}
+
+// workspace: one double per workgroup of the vector kernel (at most ew_grid's 2048), then one per
+// workgroup of the scalar kernel
+static int sumsq_slots(int64_t n, int* vec_slots) {
+  const int64_t n4 = n / 4;
+  const int vs = n4 ? ew_grid(n4, kSumsqU) : 0;
+  if (vec_slots) *vec_slots = vs;
+  return vs + kSumsqScalarBlocks;
+}
+
+extern "C" size_t hdp_grad_sumsq_workspace_bytes(int64_t n) {
+  return n > 0 ? sizeof(double) * (size_t)sumsq_slots(n, nullptr) : 0;
+}
+
+extern "C" int hdp_grad_sumsq(const float* grad, int64_t n, float grad_scale, double* out_sum, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  HDP_CHECK_ARG(n >= 0, "hdp_grad_sumsq: n < 0");
+  HDP_CHECK_ARG(out_sum && (reinterpret_cast<uintptr_t>(out_sum) & 7u) == 0,
+                "hdp_grad_sumsq: null or misaligned out_sum");
+  HDP_CHECK_ARG((reinterpret_cast<uintptr_t>(grad) & 3u) == 0, "hdp_grad_sumsq: grad not 4-byte aligned");
+  HDP_CHECK_ARG(n == 0 || grad, "hdp_grad_sumsq: null grad");
+  HDP_CHECK_ARG(n == 0 || (workspace && workspace_bytes >= hdp_grad_sumsq_workspace_bytes(n)),
+                "hdp_grad_sumsq: workspace of %zu bytes, need %zu", workspace_bytes,
+                hdp_grad_sumsq_workspace_bytes(n));
+  HDP_CHECK_ARG(n == 0 || (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0, "hdp_grad_sumsq: workspace not 8-byte aligned");
+  hipStream_t st = as_stream(stream);
+  double* part = reinterpret_cast<double*>(workspace);
+  int used = 0;
+  int64_t done = 0;
+  if (n > 0 && aligned16(grad)) {
+    const int64_t n4 = n / 4;
+    if (n4) {
+      int vs = 0;
+      sumsq_slots(n, &vs);
+      KTimer kt(K_SUMSQ, st, 4.0 * 4 * n4);
+      hipLaunchKernelGGL(grad_sumsq_kernel, dim3(vs), dim3(kEwThreads), 0, st, grad, n4, grad_scale, part);
+      used = vs;
+    }
+    HDP_CHECK_LAUNCH();
+    done = n4 * 4;
+  }
+  if (done < n) {
+    const int64_t rest = n - done;
+    int blocks = (int)((rest + kEwThreads - 1) / kEwThreads);
+    if (blocks > kSumsqScalarBlocks) blocks = kSumsqScalarBlocks;
+    {
+      KTimer kt(K_SUMSQ, st, 4.0 * rest);
+      hipLaunchKernelGGL(grad_sumsq_scalar_kernel, dim3(blocks), dim3(kEwThreads), 0, st, grad, done, n, grad_scale,
+                         part + used);
+    }
+    HDP_CHECK_LAUNCH();
+    used += blocks;
+  }
+  {
+    KTimer kt(K_CLIP_FINISH, st, 8.0 * used);
+    hipLaunchKernelGGL(sum_f64_kernel, dim3(1), dim3(kEwThreads), 0, st, part, used, out_sum);
+  }
+  HDP_CHECK_LAUNCH();
+  return HDP_OK;
+}
+
+extern "C" int hdp_clip_finish(const double* sums, int nsums, float max_norm, hdp_clip_state* state, void* stream) {
+  HDP_CHECK_ARG(nsums >= 0, "hdp_clip_finish: nsums < 0");
+  HDP_CHECK_ARG(state, "hdp_clip_finish: null state");
+  HDP_CHECK_ARG((reinterpret_cast<uintptr_t>(state) & 7u) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7u) == 0,
+                "hdp_clip_finish: state and sums must be 8-byte aligned");
+  HDP_CHECK_ARG(nsums == 0 || sums, "hdp_clip_finish: null sums");
+  HDP_CHECK_ARG(max_norm > 0.f, "hdp_clip_finish: max_norm must be > 0 (got %g)", (double)max_norm);
+  hipStream_t st = as_stream(stream);
+  {
+    KTimer kt(K_CLIP_FINISH, st, 8.0 * nsums);
+    hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(kEwThreads), 0, st, sums, nsums, max_norm, state);
+  }
+  HDP_CHECK_LAUNCH();
   return HDP_OK;
 }
 

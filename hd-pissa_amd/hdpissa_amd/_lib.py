@@ -46,7 +46,25 @@ class CopyItem(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
 
 
-COPY_GROUP_MAX = 170  # non-empty items per launch of hdp_copy_group (its kernel-argument block)
+class ClipState(ctypes.Structure):
+    """hdp_clip_state (include/hdpissa.h): the 32-byte device record of one step's gradient norm."""
+    _fields_ = [("sumsq", ctypes.c_double), ("norm", ctypes.c_float), ("coef", ctypes.c_float),
+                ("skip", ctypes.c_int32), ("skipped_total", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+CLIP_STATE_BYTES = 32
+assert ctypes.sizeof(ClipState) == CLIP_STATE_BYTES
+
+
+def clip_record(raw) -> dict:
+    """A clip record's 32 bytes (any bytes-like host copy) as {"sumsq", "norm", "coef", "skipped",
+    "skipped_total"}."""
+    s = ClipState.from_buffer_copy(bytes(raw))
+    return {"sumsq": s.sumsq, "norm": s.norm, "coef": s.coef, "skipped": bool(s.skip),
+            "skipped_total": int(s.skipped_total)}
+
+
+COPY_GROUP_MAX = 170 # non-empty items per launch of hdp_copy_group (its kernel-argument block)
 
 
 class SvdItem(ctypes.Structure):
@@ -74,6 +92,11 @@ SIGNATURES = {
     "hdp_copy_group": (_c_int, [_c_int, ctypes.POINTER(CopyItem), _c_vp]),
     "hdp_adam_factors": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
                                   _c_f, _c_f, _c_f, _c_int, _c_vp]),
+    "hdp_grad_sumsq_workspace_bytes": (_c_sz, [_c_i64]),
+    "hdp_grad_sumsq": (_c_int, [_c_vp, _c_i64, _c_f, _c_vp, _c_vp, _c_sz, _c_vp]),
+    "hdp_clip_finish": (_c_int, [_c_vp, _c_int, _c_f, _c_vp, _c_vp]),
+    "hdp_adam_factors_clip": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                       _c_f, _c_f, _c_f, _c_int, _c_vp, _c_vp]),
     "hdp_delta_gemm": (_c_int, [_c_i64, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64,
                                 _c_vp, _c_int, _c_int, _c_int, _c_vp]),
     "hdp_delta_set_math": (_c_int, [_c_int]),
@@ -83,7 +106,9 @@ SIGNATURES = {
     "hdp_delta_plan_run": (_c_int, [_c_vp, _c_vp]),
     "hdp_delta_plan_fused_adam": (_c_int, [_c_vp]),
     "hdp_delta_plan_run_adam": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp] + [ctypes.c_float] * 10 + [_c_int, _c_vp]),
-    "hdp_delta_plan_fused_fallback": (_c_int, [_c_vp, ctypes.POINTER(_c_int)]),
+    "hdp_delta_plan_run_adam_clip": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp] + [ctypes.c_float] * 10
+                                     + [_c_int, _c_vp, _c_vp]),
+    "hdp_delta_plan_fused_fallback":(_c_int, [_c_vp, ctypes.POINTER(_c_int)]),
     "hdp_delta_plan_invalidate": (_c_int, [_c_vp]),
     "hdp_delta_plan_tiles": (_c_int, [_c_vp, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_int)]),
     "hdp_delta_plan_math": (_c_int, [_c_vp]),

@@ -43,6 +43,15 @@ def _f32(*ts):
             raise TypeError(f"expected float32, got {t.dtype}")
 
 
+def _clip_ptr(state: torch.Tensor) -> int:
+    """Device pointer of a clip record (hdp_clip_state): 32 contiguous bytes, 8-byte aligned."""
+    _need_gpu(state)
+    if state.dtype != torch.uint8 or state.numel() != _lib.CLIP_STATE_BYTES or not state.is_contiguous() \
+            or state.data_ptr() % 8:
+        raise ValueError("clip state: a contiguous, 8-byte aligned uint8 tensor of 32 bytes (HipOps.clip_state)")
+    return state.data_ptr()
+
+
 class HipOps:
     """The MI355X kernel set (libhdpissa.so)."""
 
@@ -264,15 +273,54 @@ class HipOps:
 
     # -- K3 --------------------------------------------------------------------------------
     def adam(self, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, delta: torch.Tensor, t: int, lr: float,
-             beta1: float, beta2: float, eps: float, zero_grad: bool, grad_scale: float = 1e16) -> None:
+             beta1: float, beta2: float, eps: float, zero_grad: bool, grad_scale: float = 1e16,
+             clip: Optional[torch.Tensor] = None) -> None:
+        """K3.  ``clip``: the step's clip record (``clip_finish``) -- Adam runs on the clipped gradient,
+        or leaves m / v alone and writes delta = 0 if the record says skip; None: the plain step."""
         _need_gpu(grad, m, v, delta)
         _f32(grad, m, v, delta)
         n = grad.numel()
         if not (m.numel() == v.numel() == delta.numel() == n):
             raise ValueError("adam: size mismatch")
         s = adam_scalars(t, lr, beta1, beta2, eps, grad_scale)
+        if clip is not None:
+            check(lib().hdp_adam_factors_clip(grad.data_ptr(), m.data_ptr(), v.data_ptr(), delta.data_ptr(), n, *s,
+                                              int(bool(zero_grad)), _clip_ptr(clip), _stream()),
+                  "hdp_adam_factors_clip")
+            return
         check(lib().hdp_adam_factors(grad.data_ptr(), m.data_ptr(), v.data_ptr(), delta.data_ptr(), n, *s,
                                      int(bool(zero_grad)), _stream()), "hdp_adam_factors")
+
+    # -- gradient-norm clipping ------------------------------------------------------------
+    def clip_state(self, device) -> torch.Tensor:
+        """A zeroed clip record (hdp_clip_state, 32 bytes) in device memory."""
+        return torch.zeros(_lib.CLIP_STATE_BYTES, dtype=torch.uint8, device=device)
+
+    def grad_sumsq(self, grad: torch.Tensor, out: torch.Tensor, grad_scale: float = 1e16) -> None:
+        """out[0] (float64) = sum over grad of double(float32(g * grad_scale))^2: one streaming read,
+        float64 accumulation, bitwise repeatable (hdp_grad_sumsq)."""
+        _need_gpu(grad, out)
+        _f32(grad)
+        if out.dtype != torch.float64 or out.numel() < 1:
+            raise TypeError("grad_sumsq: out must hold one float64")
+        if not grad.is_contiguous():
+            raise ValueError("grad_sumsq: grad must be contiguous")
+        n = grad.numel()
+        nb = lib().hdp_grad_sumsq_workspace_bytes(n)
+        ws = self._workspace("sumsq", nb, grad.device)
+        check(lib().hdp_grad_sumsq(grad.data_ptr(), n, float(grad_scale), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _stream()), "hdp_grad_sumsq")
+
+    def clip_finish(self, sums: torch.Tensor, max_norm: float, state: torch.Tensor) -> None:
+        """state <- the clip record of sum(sums) (float64, added in index order) under ``max_norm`` > 0
+        (``math.inf``: measure and guard only): norm, coef = min(1, max_norm / (norm + 1e-6)), skip."""
+        _need_gpu(sums, state)
+        if sums.dtype != torch.float64 or not sums.is_contiguous():
+            raise TypeError("clip_finish: sums must be a contiguous float64 tensor")
+        if not (float(max_norm) > 0.0):
+            raise ValueError("clip_finish: max_norm must be > 0")
+        check(lib().hdp_clip_finish(sums.data_ptr(), sums.numel(), float(max_norm), _clip_ptr(state), _stream()),
+              "hdp_clip_finish")
 
     # -- K4 --------------------------------------------------------------------------------
     def delta_gemm(self, out: int, inn: int, r: int, nseg: int, dA: torch.Tensor, dB: torch.Tensor,
@@ -437,9 +485,11 @@ class DeltaPlan:
         return bool(self._lib.hdp_delta_plan_fused_adam(self._h))
 
     def run_adam(self, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, delta: torch.Tensor, t: int, lr: float,
-                 beta1: float, beta2: float, eps: float, zero_grad: bool, grad_scale: float = 1e16) -> None:
+                 beta1: float, beta2: float, eps: float, zero_grad: bool, grad_scale: float = 1e16,
+                 clip: Optional[torch.Tensor] = None) -> None:
         """K3 over the plan's factor entries folded into its K4 run (hp:356-373 + hp:389-394): the
-        arenas' bases (the items' dA / dB point into ``delta``); m, v, delta as ``adam`` computes them."""
+        arenas' bases (the items' dA / dB point into ``delta``); m, v, delta as ``adam`` computes them
+        (``clip``: under the step's clip record, as ``adam(clip=)``)."""
         _need_gpu(grad, m, v, delta)
         _f32(grad, m, v, delta)
         D = adam_delta_bound(t, lr, beta1, beta2)
@@ -451,6 +501,11 @@ class DeltaPlan:
             # the factors changed in place since the constant panel halves / maxima were packed
             check(self._lib.hdp_delta_plan_invalidate(self._h), "hdp_delta_plan_invalidate")
         self._factor_versions = vers
+        if clip is not None:
+            check(self._lib.hdp_delta_plan_run_adam_clip(self._h, grad.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                                         delta.data_ptr(), *s, D, int(bool(zero_grad)),
+                                                         _clip_ptr(clip), _stream()), "hdp_delta_plan_run_adam_clip")
+            return
         check(self._lib.hdp_delta_plan_run_adam(self._h, grad.data_ptr(), m.data_ptr(), v.data_ptr(), delta.data_ptr(),
                                                 *s, D, int(bool(zero_grad)), _stream()), "hdp_delta_plan_run_adam")
 

@@ -28,6 +28,17 @@ merge -- ~48 N Wn bytes of HBM traffic per rank.  Here, per arena (a
                  others: the replicas are bitwise equal in both dtypes.  World size 1: the gather path.
   3. A.grad = B.grad = None  (hp:397-398).
 
+Opt-in, off by default (``max_grad_norm=``; the reference has neither): global gradient-norm clipping and
+the non-finite-step skip, decided on the device.  In front of step 1, over the collected gradients of ALL
+arenas: one sum-of-squares launch per arena (float64 accumulation of (grad x 1e16)^2), at Wn > 1 one
+all-gather of those few bytes (the ranks own disjoint singular components: the global norm is the norm of
+the whole adapter gradient, and every rank sums the same values in the same rank-major order), one finish
+launch that writes the clip record {sumsq, norm, coef = min(1, c / (norm + 1e-6)), skip} -- and K3 / the
+fused Adam-pack read that record in stream order, as they read the probe's error word: Adam runs on
+(grad x 1e16) x coef; a non-finite sum leaves m and v alone and writes delta = 0, so the merge adds exactly
+0 to W_res.  No host synchronisation.  ``t`` still advances on a skipped step: the bias corrections of the
+following steps run one step ahead of the moments.
+
 Semantics kept from the reference: Adam without weight decay, bias correction with the
 post-increment t (hp:350), A and B never updated (hp:375-376; the deltas are recomputed
 against the *initial* factors every step), grads scaled x1e16 (hp:356-357), bf16 models
@@ -188,7 +199,7 @@ class HDPissaStep:
 
     def __init__(self, model: nn.Module, world_size: int, rank: int = 0, comm=None, ops=None,
                  exchange: str = "gather", bucket_bytes: Optional[int] = None, beta1: float = 0.9,
-                 beta2: float = 0.999, eps: float = 1e-8):
+                 beta2: float = 0.999, eps: float = 1e-8, max_grad_norm: Optional[float] = None):
         if exchange not in ("gather", "allreduce", "shard"):
             raise ValueError("exchange must be 'gather', 'allreduce' or 'shard'")
         self.layers = [m for _, m in custom_layers(model)]
@@ -230,6 +241,45 @@ class HDPissaStep:
         # 3.7 / 5.3 / 8.5 ms for per-module f32 launches)
         self.grouped_multiseg = self.grouped
         self._fuse_adam = os.environ.get("HDP_FUSED_ADAM", "1") != "0"
+        # global gradient-norm clipping + non-finite-step skip (off by default: nothing below is built or
+        # launched then).  c > 0; math.inf = measure and guard only
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.clip_state: Optional[torch.Tensor] = None   # the device record (hdp_clip_state, 32 bytes)
+        if self.max_grad_norm is not None:
+            if not self.max_grad_norm > 0.0:  # (NaN fails too)
+                raise ValueError("max_grad_norm must be > 0 (math.inf: measure the norm and guard only)")
+            if not (hasattr(ops, "grad_sumsq") and hasattr(ops, "clip_finish")):
+                raise NotImplementedError(f"the op set {getattr(ops, 'name', ops)!r} has no grad_sumsq / clip_finish: "
+                                          "max_grad_norm needs the fused device-side norm")
+            make = getattr(ops, "clip_state", None)
+            self.clip_state = make(self.device) if make is not None else \
+                torch.zeros(32, dtype=torch.uint8, device=self.device)
+            # per-arena sums, padded to 16 bytes (the all-gather's unit; the pad stays 0.0, which the
+            # finish's in-order sum passes over), and at Wn > 1 every rank's copy of them, rank-major
+            n = -(-len(self.plans) // 2) * 2
+            self._sums = torch.zeros(n, dtype=torch.float64, device=self.device)
+            self._sums_all = torch.zeros(world_size * n, dtype=torch.float64, device=self.device) \
+                if world_size > 1 else self._sums
+
+    def clip_info(self) -> dict:
+        """The clip record of the last step, read back (this synchronises): {"norm", "coef", "skipped",
+        "skipped_total"} (and "sumsq")."""
+        if self.clip_state is None:
+            raise RuntimeError("clip_info: the stepper was built without max_grad_norm")
+        from ._lib import clip_record
+        return clip_record(self.clip_state.cpu().numpy().tobytes())
+
+    def _clip_record(self) -> torch.Tensor:
+        """Gradient norm of every arena (every rank's) -> the clip record, all on the current stream."""
+        ops = self.ops
+        for plan in self.plans:
+            self._collect_grads(plan.arena)
+        for i, plan in enumerate(self.plans):
+            ops.grad_sumsq(plan.arena.grad, self._sums[i:i + 1])
+        if self.world_size > 1:
+            self.comm.allgather_any(self._sums.view(torch.uint8), self._sums_all.view(torch.uint8))
+        ops.clip_finish(self._sums_all, self.max_grad_norm, self.clip_state)
+        return self.clip_state
 
     def invalidate_factors(self) -> None:
         """The factors A / B were rewritten in place in a way the arena's version counter does not see
@@ -274,25 +324,31 @@ class HDPissaStep:
                 from ._lib import HdpError
                 raise HdpError("probe kernels reported a failed hand-off (hdp_probe_errors); the "
                                "accumulated gradients are not trustworthy -- step refused")
+            clip = self._clip_record() if self.max_grad_norm is not None else None
             for plan in self.plans:
-                self._step_arena(plan, lr, t)
+                self._step_arena(plan, lr, t, clip)
         for L in self.layers:  # hp:397-398
             prm = L._parameters
             prm["A"].grad = None
             prm["B"].grad = None
 
-    def _step_arena(self, plan: _ArenaPlan, lr: float, t: int) -> None:
+    def _step_arena(self, plan: _ArenaPlan, lr: float, t: int, clip: Optional[torch.Tensor] = None) -> None:
         arena, ops, Wn = plan.arena, self.ops, self.world_size
-        self._collect_grads(arena)
+        kw = {}
+        if clip is not None:
+            kw["clip"] = clip  # (the gradients of every arena were collected for the norm)
+        else:
+            self._collect_grads(arena)
         fused = self._fused_plans(plan, lr, t)
         if fused is not None:
             # K3 folded into K4's operand preparation -- per plan one Adam pass that also
             # writes the delta halves of the H2 panels, then the merge (no standalone Adam / pack)
             for p, _ in fused:
                 p.run_adam(arena.grad, arena.m, arena.v, arena.delta, t, lr, self.beta1, self.beta2, self.eps,
-                           zero_grad=True)
+                           zero_grad=True, **kw)
             return
-        ops.adam(arena.grad, arena.m, arena.v, arena.delta, t, lr, self.beta1, self.beta2, self.eps, zero_grad=True)
+        ops.adam(arena.grad, arena.m, arena.v, arena.delta, t, lr, self.beta1, self.beta2, self.eps, zero_grad=True,
+                 **kw)
         if self.exchange == "gather" or (self.exchange == "shard" and Wn == 1):
             self._gather(plan)
         elif self.exchange == "shard":
@@ -559,13 +615,16 @@ _STEPPERS: Dict[int, HDPissaStep] = {}
 
 def hd_pissa_step(model: nn.Module, lr: float, t: int, world_size: int, rank: int = 0, beta1: float = 0.9,
                   beta2: float = 0.999, epsilon: float = 1e-8, exchange: str = "gather", comm=None,
-                  ops=None) -> HDPissaStep:
+                  ops=None, max_grad_norm: Optional[float] = None) -> HDPissaStep:
     """Functional form of the reference block hp:352-398 (one call per optimizer step).
-    The step object (plan, buffers, streams) is cached per model."""
+    The step object (plan, buffers, streams) is cached per model.  ``max_grad_norm``: clip the global
+    gradient norm and skip non-finite steps on the device (HDPissaStep; None, the default: the reference's
+    step)."""
     st = _STEPPERS.get(id(model))
-    if st is None or st.exchange != exchange:
+    mgn = None if max_grad_norm is None else float(max_grad_norm)
+    if st is None or st.exchange != exchange or st.max_grad_norm != mgn:
         st = HDPissaStep(model, world_size, rank, comm=comm, ops=ops, exchange=exchange, beta1=beta1, beta2=beta2,
-                         eps=epsilon)
+                         eps=epsilon, max_grad_norm=max_grad_norm)
         _STEPPERS[id(model)] = st
     st.step(lr, t)
     return st

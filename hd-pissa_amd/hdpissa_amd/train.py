@@ -12,6 +12,12 @@ Changed: the reference all-reduces the loss and reads it bac
 for logging only (the gradients do not depend on it).  Here, by default (``loss_sync="step"``),
 the micro-batch losses are summed on the device in float64 and reduced / read back once per
 optimizer step; ``loss_sync="micro"`` reproduces the reference's per-micro-step cadence.
+
+Added (opt-in, ``max_grad_norm=``; the reference does not clip): the step clips the global gradient norm
+and skips a non-finite step on the device (HDPissaStep).  ``grad_norm_list`` then holds the norm of every
+optimizer step and ``skipped_steps`` the running count of skipped ones.  With ``loss_sync="step"`` the
+loss read-back moves behind the step and fetches the step's clip record in the same transfer: still one
+synchronisation per optimizer step.
 """
 from __future__ import annotations
 
@@ -29,7 +35,8 @@ class HDPissaTrainer:
     def __init__(self, model: nn.Module, world_size: int, rank: int, lr: float, total_steps: int,
                  accumulation_steps: int = 1, warmup_steps: int = 0, warmup_ratio: float = 0.0,
                  schedule: str = "cosine", exchange: str = "gather", loss_sync: str = "step", comm=None, ops=None,
-                 beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+                 beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
+                 max_grad_norm: Optional[float] = None):
         if loss_sync not in ("step", "micro"):
             raise ValueError("loss_sync must be 'step' or 'micro'")
         if accumulation_steps < 1:
@@ -46,7 +53,10 @@ class HDPissaTrainer:
         self.accumulation_steps = accumulation_steps
         self.loss_sync = loss_sync
         self.stepper = HDPissaStep(model, world_size, rank, comm=comm, ops=ops, exchange=exchange, beta1=beta1,
-                                   beta2=beta2, eps=eps)
+                                   beta2=beta2, eps=eps, max_grad_norm=max_grad_norm)
+        self.max_grad_norm = self.stepper.max_grad_norm
+        self.grad_norm_list: List[float] = []   # per optimizer step (max_grad_norm set)
+        self.skipped_steps = 0                  # optimizer steps skipped for a non-finite gradient norm
         self.t = 0                 # optimizer steps taken (hp:300, 350)
         self.micro = 0             # micro-batches seen in the current epoch (the reference's i)
         self.loss_list: List[float] = []
@@ -82,6 +92,8 @@ class HDPissaTrainer:
         return True
 
     def optimizer_step(self) -> None:
+        if self.max_grad_norm is not None:
+            return self._optimizer_step_clipped()
         if self.loss_sync == "micro":
             acc = self._acc_host
         else:
@@ -91,6 +103,30 @@ class HDPissaTrainer:
         self.lr_list.append(lr)
         self.t += 1                                           # hp:350
         self.stepper.step(lr, self.t)                         # hp:352-398
+        self._acc_host, self._acc_dev = 0.0, None             # hp:400
+
+    def _optimizer_step_clipped(self) -> None:
+        """optimizer_step with the clip record: the step first, then ONE read-back that brings the window's
+        loss (loss_sync="step") and the record of the step that just ran."""
+        from ._lib import clip_record
+        acc_dev = None
+        if self.loss_sync == "step" and self._acc_dev is not None:
+            acc_dev = self._reduce(self._acc_dev).reshape(1)   # (enqueued before the step, read after it)
+        lr = lr_at(self.t, self.initial_lr, self.warmup_steps, self.total_steps, self.schedule)  # hp:338-344
+        self.t += 1                                           # hp:350
+        self.stepper.step(lr, self.t)                         # hp:352-398
+        rec = self.stepper.clip_state
+        if acc_dev is not None:
+            raw = torch.cat([rec, acc_dev.to(rec.device).view(torch.uint8)]).cpu()
+            acc = float(raw[rec.numel():].view(torch.float64).item()) / self.world_size
+        else:
+            raw = rec.cpu()
+            acc = self._acc_host if self.loss_sync == "micro" else 0.0
+        info = clip_record(raw[:rec.numel()].numpy().tobytes())
+        self.loss_list.append(acc)                            # hp:336
+        self.lr_list.append(lr)
+        self.grad_norm_list.append(info["norm"])
+        self.skipped_steps = info["skipped_total"]
         self._acc_host, self._acc_dev = 0.0, None             # hp:400
 
     def train_epoch(self, dataloader, epoch: int = 0) -> List[float]:

@@ -117,6 +117,52 @@ int hdp_adam_factors(float* grad, float* m, float* v, float* delta, int64_t n, f
                      float bc1, float bc2, float lr, float eps, int zero_grad, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Global gradient-norm clipping and the non-finite-step skip (opt-in; the reference has neither: with
+ * no clip record the step is hp:352-398 unchanged).  The optimizer step merges its update into W_res in
+ * place, so a bad gradient is refused BEFORE Adam, on the device, with no host synchronisation:
+ *   gs    = float32(grad * grad_scale)                     the product K3 forms (hp:356-357)
+ *   sumsq = sum double(gs)^2                               over every entry of every arena (every rank's)
+ *   norm  = float32(sqrt(sumsq))
+ *   coef  = min(1.0f, float32(max_norm) / (norm + 1e-6f))  torch.nn.utils.clip_grad_norm_'s arithmetic
+ * and Adam runs on gs * coef (its own float32 multiply; gs * 1.0f is exact, so an unclipped step keeps
+ * the bits of the step without a record).  If sumsq is not finite the step is skipped: m and v stay,
+ * delta = 0 (the merge adds exactly 0), grad is cleared when zero_grad is set, skipped_total grows by one.
+ * The caller's step counter still advances: the bias corrections of the following steps then run one
+ * step ahead of the moments.
+ * The record lives in device memory, is owned by the caller and is written only by hdp_clip_finish; the
+ * Adam kernels read it in stream order, once per workgroup.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+  double sumsq;          /* the global sum of squares of the scaled gradients */
+  float norm;            /* float32(sqrt(sumsq)) */
+  float coef;            /* min(1, max_norm / (norm + 1e-6)); 1 on a skipped step */
+  int32_t skip;          /* 1: sumsq was not finite, this step applies no update */
+  int32_t skipped_total; /* cumulative count of skipped steps */
+  int32_t reserved[2];
+} hdp_clip_state;
+#if defined(__cplusplus)
+static_assert(sizeof(hdp_clip_state) == 32, "hdp_clip_state is a 32-byte record");
+#else
+_Static_assert(sizeof(hdp_clip_state) == 32, "hdp_clip_state is a 32-byte record");
+#endif
+/* *out_sum (one double, device) = sum over the n float32 entries of double(float32(grad[i] * grad_scale))^2.
+ * A streaming read (4 B per entry) with float64 accumulation per lane, a fixed-order reduction per
+ * workgroup into one workspace slot each, and an in-order sum of the slots: no floating-point atomics,
+ * so the same input gives the same bits on every run.  workspace: device scratch of
+ * hdp_grad_sumsq_workspace_bytes(n) bytes.  n == 0 writes 0. */
+size_t hdp_grad_sumsq_workspace_bytes(int64_t n);
+int hdp_grad_sumsq(const float* grad, int64_t n, float grad_scale, double* out_sum, void* workspace,
+                   size_t workspace_bytes, void* stream);
+/* state <- the record of sum(sums[0 .. nsums)) (device doubles, added in index order: the per-arena and
+ * per-rank sums) under max_norm > 0 (+inf: measure and guard only).  nsums == 0 gives sumsq 0, coef 1. */
+int hdp_clip_finish(const double* sums, int nsums, float max_norm, hdp_clip_state* state, void* stream);
+/* hdp_adam_factors under a clip record (clip == NULL: hdp_adam_factors itself) */
+int hdp_adam_factors_clip(float* grad, float* m, float* v, float* delta, int64_t n, float grad_scale,
+                          float beta1, float one_minus_beta1, float beta2, float one_minus_beta2,
+                          float bc1, float bc2, float lr, float eps, int zero_grad,
+                          const hdp_clip_state* clip, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * K4 delta GEMM -- replaces hp:389-394 (zeros_like, the per-rank loop of 3 GEMMs, merge).
  * For one module (out x in) and nseg rank segments i = 0..nseg-1:
  *   dW = 0; for i: dW -= dB_i @ (A_i - dA_i) + B_i @ dA_i       (== hp:392's bracket)
@@ -202,6 +248,13 @@ int hdp_delta_plan_fused_adam(hdp_delta_plan plan);
 int hdp_delta_plan_run_adam(hdp_delta_plan plan, float* grad, float* m, float* v, float* delta, float grad_scale,
                             float beta1, float one_minus_beta1, float beta2, float one_minus_beta2, float bc1,
                             float bc2, float lr, float eps, float delta_bound, int zero_grad, void* stream);
+/* run_adam under a clip record (hdp_clip_state above; clip == NULL: run_adam itself): the folded Adam
+ * scales by coef and skips like hdp_adam_factors_clip -- on a skipped step every delta is 0, the delta
+ * panel halves are packed from zeros and the merge leaves W as it was. */
+int hdp_delta_plan_run_adam_clip(hdp_delta_plan plan, float* grad, float* m, float* v, float* delta,
+                                 float grad_scale, float beta1, float one_minus_beta1, float beta2,
+                                 float one_minus_beta2, float bc1, float bc2, float lr, float eps,
+                                 float delta_bound, int zero_grad, const hdp_clip_state* clip, void* stream);
 /* 1 if the last run_adam took the live-factor fallback (synchronises; tests / diagnosis) */
 int hdp_delta_plan_fused_fallback(hdp_delta_plan plan, int* taken);
 /* run_adam packs the CONSTANT operand halves (B, and the max |A| / max |B| scale bounds) once per plan
