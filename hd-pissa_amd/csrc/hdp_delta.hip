@@ -40,27 +40,10 @@
 #include <vector>
 
 #include "hdp_common.h"
+#include "hdp_delta_plan.h"  // DeltaArgs, kDT, kPanel / kPanelH, the table offsets, and the host plan
 
 namespace hdp {
 
-struct DeltaArgs {
-  int64_t out, in;
-  int r, nseg;
-  const float* dA;
-  const float* dB;
-  int64_t dstr;
-  const float* A;
-  const float* B;
-  int64_t fstr;
-  void* dst;
-  int vec_l;   // L rows 16-B aligned (r % 4 == 0, aligned bases and strides)
-  int vec_r;   // R rows 16-B aligned (in % 4 == 0, aligned bases and strides)
-  __bf16* limg;  // packed bf16x3 panels (plans with x3 math; see MX3P), else null
-  __bf16* rimg;  //   (fp16x2 panels for H2 plans: the same pointers reinterpreted)
-  float* ktab;   // H2 plans: the item's per-k scale table (see H2 below), else null
-};
-
-constexpr int kDT = 128;             // workgroup tile (both dims)
 constexpr int kSC = 16;              // steps per chunk -> 32 k-slots (16 dB|A-dA, 16 B|dA)
 constexpr int kLDS = 2 * 32 * kDT;   // floats per buffer: L [32][128] + R [32][128]
 
@@ -359,7 +342,7 @@ struct MX3 {
 struct StageX3P {
   f32x4 v[6];
 };
-constexpr int kPanel = 3 * kDT * 16;  // bf16 elements per packed panel
+static_assert(MX3::kSteps == kX3Steps, "the plan header's chunk arithmetic (k4_chunks)");
 
 struct MX3P {
   static constexpr int kSteps = MX3::kSteps;
@@ -1154,7 +1137,9 @@ template <int DEF> struct X3WDefer {
   // that tile's own accumulators move to `pend`
   static constexpr int min_chunks = span + 1;
 };
-template <int DEF> int x3w_defer_min_chunks() { return X3WDefer<DEF>::min_chunks; }
+static_assert(X3WDefer<1>::min_chunks == k4_defer_min_chunks(1) && X3WDefer<2>::min_chunks == k4_defer_min_chunks(2) &&
+                  X3WDefer<4>::min_chunks == k4_defer_min_chunks(4),
+              "the plan header's minimum chunk counts");
 
 // the row offsets are recomputed per access from scalars made opaque here: hoisted out of
 // the tile loop they would take 64 SGPRs (the kernel has none to spare)
@@ -1500,19 +1485,7 @@ __global__ __launch_bounds__(512, 1) void delta_x3w_kernel(const DeltaArgs* __re
 // panels, and delta_h2_kernel runs the wide schedule on them with K = 32 per chunk.
 // ---------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-constexpr int kPanelH = 2 * kDT * 16;  // fp16 elements per H2 panel: [2 parts][128][16 k]
-// per-item table (floats): [0] = 2^-E, [4 ..) sl[K], then sr[K], then the scale pass's
-// partial maxima: L [seg][ceil(out / 256)][2r], R [seg][ceil(in / 256)][2r]; with
-// k = (2 seg + half) r + step (half 0: dB | A - dA, half 1: B | dA)
-static inline int64_t h2_tab_floats(int64_t out, int64_t in, int r, int nseg) {
-  const int64_t K = 2ll * r * nseg;
-  return 4 + 2 * K + (int64_t)nseg * ((out + 255) / 256 + (in + 255) / 256) * 2 * r + 2 * r;
-}
-// the fused Adam + pack path (single-segment plans): constant maxima max_o |B[o][k]| (r floats), then
-// max_c |A[k][c]| (r floats), behind the scale pass's partials
-__host__ __device__ inline int64_t h2_cmax_off(int64_t out, int64_t in, int r, int nseg) {
-  return 4 + 4ll * r * nseg + (int64_t)nseg * ((out + 255) / 256 + (in + 255) / 256) * 2 * r;
-}
+// (kPanelH, the per-item table h2_tab_floats and the constant maxima h2_cmax_off: hdp_delta_plan.h)
 
 // partial maxima of |L| per column and |R| per row: one workgroup per (item, segment, side,
 // 256 rows of L or 256 columns of R), one row / column per thread
@@ -1852,11 +1825,7 @@ __global__ __launch_bounds__(256) void k4_h2_bound_kernel(const DeltaArgs* __res
 // 8 k8 + 7], an R thread rows 8 k8 .. 8 k8 + 7 of dA at 4 columns -- so each writes WHOLE 16-B panel granules
 // (8 k-slots of one half) instead of two scattered 8-B halves, and an R thread both halves of its panel rows
 // (A - dA and dA: the full 32-B row per plane, contiguous over consecutive threads)
-static inline int64_t h2_ap_threads(int64_t out, int64_t in, int r) {
-  if (r % 8 == 0) return out * (r / 8) + (in + 3) / 4 * (r / 8);
-  const int64_t qr = (r + 3) / 4;
-  return out * qr + (in + 3) / 4 * qr;
-}
+// (h2_ap_threads, hdp_delta_plan.h)
 
 // CLIP: under a clip record (hdp_clip_state) -- its skip flag joins the refusal and its coefficient scales
 // the gradient (adam1_clip); without one the kernel is the instruction sequence it always was
@@ -2652,55 +2621,9 @@ __global__ __launch_bounds__(512, 1) void delta_h2_kernel(const DeltaArgs* __res
   __builtin_amdgcn_s_waitcnt(vmcnt_imm(0));  // no LDS-DMA outstanding when the workgroup retires
 }
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-// validate one module's operands and fill its descriptor (shared by both entry points)
-static int make_args(const char* who, int64_t out, int64_t in, int r, int nseg, const float* dA, const float* dB,
-                     int64_t delta_seg_stride, const float* A, const float* B, int64_t factor_seg_stride, void* dst,
-                     int dst_dtype, int mode, int round_bf16, DeltaArgs& a) {
-  HDP_CHECK_ARG(out > 0 && in > 0 && r > 0 && nseg > 0, "%s: bad shape out=%lld in=%lld r=%d nseg=%d", who,
-                (long long)out, (long long)in, r, nseg);
-  HDP_CHECK_ARG(out * in * (dst_dtype == HDP_BF16 && mode == HDP_DW_MERGE ? 2 : 4) < ((int64_t)1 << 31),
-                "%s: matrix too large (%lld x %lld; the kernel addresses one module's dst with 31-bit offsets)", who,
-                (long long)out, (long long)in);
-  HDP_CHECK_ARG(dA && dB && A && B && dst, "%s: null pointer", who);
-  HDP_CHECK_ARG(mode == HDP_DW_STORE || mode == HDP_DW_MERGE, "%s: bad mode %d", who, mode);
-  HDP_CHECK_ARG(dst_dtype == HDP_F32 || dst_dtype == HDP_BF16, "%s: bad dtype %d", who, dst_dtype);
-  HDP_CHECK_ARG(mode == HDP_DW_MERGE || dst_dtype == HDP_F32, "%s: STORE mode writes float32", who);
-  HDP_CHECK_ARG(!(round_bf16 && mode == HDP_DW_MERGE && dst_dtype == HDP_F32),
-                "%s: round_bf16 applies to bf16 W_res (or STORE), not to a float32 merge", who);
-  HDP_CHECK_ARG(nseg == 1 || (delta_seg_stride > 0 && factor_seg_stride > 0), "%s: segment strides must be positive",
-                who);
-  a.out = out;
-  a.in = in;
-  a.r = r;
-  a.nseg = nseg;
-  a.dA = dA;
-  a.dB = dB;
-  a.dstr = delta_seg_stride;
-  a.A = A;
-  a.B = B;
-  a.fstr = factor_seg_stride;
-  a.dst = dst;
-  const bool strides4 = nseg == 1 || (delta_seg_stride % 4 == 0 && factor_seg_stride % 4 == 0);
-  a.vec_l = (r % 4 == 0) && al16(dB) && al16(B) && strides4;
-  a.vec_r = (in % 4 == 0) && al16(dA) && al16(A) && strides4;
-  a.limg = a.rimg = nullptr;
-  a.ktab = nullptr;
-  return HDP_OK;
-}
-
-// algorithmic work of one module: dst written (and W read for MERGE) once + the 4 factor
-// operands once; 4 r nseg flop per element
-static double args_bytes(const DeltaArgs& a, int mode, int dst_dtype) {
-  const double wes = (mode == HDP_DW_MERGE && dst_dtype == HDP_BF16) ? 2.0 : 4.0;
-  return (double)a.out * a.in * (mode == HDP_DW_MERGE ? 2.0 * wes : 4.0) + 8.0 * a.r * (a.out + a.in) * a.nseg;
-}
-static double args_flops(const DeltaArgs& a) { return 4.0 * a.out * a.in * a.r * a.nseg; }
-static int64_t args_tiles(const DeltaArgs& a, int tr = kDT) { return ((a.out + tr - 1) / tr) * ((a.in + kDT - 1) / kDT); }
-
-// K4 math selection (hdp_delta_set_math / HDP_K4_MATH=auto|f32|x3): AUTO takes the exact
-// f32 MFMA while K4 is HBM-bound (K = 2 r nseg <= 32) and the bf16x3 split above that.
+// The knobs of a plan (K4Knobs, hdp_delta_plan.h).  Math (hdp_delta_set_math / HDP_K4_MATH=auto|f32|x3|h2) and
+// the x3 staging (hdp_delta_set_x3_stage / HDP_K4_X3_STAGE=wide|glds|regs) are read from the environment
+// once per process and overridden by their setters; the others are read at every plan creation.
 static int g_math = -1;
 static int k4_math() {
   if (g_math < 0) {
@@ -2712,22 +2635,93 @@ static int k4_math() {
   }
   return g_math;
 }
-// x3 plan kernel (HDP_K4_X3_STAGE): wide = delta_x3w_kernel (default), glds = delta_x3g_kernel,
-// regs = delta_x3p_kernel
-enum { X3_REGS = 0, X3_GLDS = 1, X3_WIDE = 2 };
-static int g_stage = -1;  // hdp_delta_set_x3_stage overrides the env
+static int g_stage = -1;
 static int x3_stage() {
   if (g_stage < 0) {
     const char* e = getenv("HDP_K4_X3_STAGE");
-    g_stage = X3_WIDE;
-    if (e && e[0] == 'r') g_stage = X3_REGS;
-    if (e && e[0] == 'g') g_stage = X3_GLDS;
+    g_stage = HDP_X3_WIDE;
+    if (e && e[0] == 'r') g_stage = HDP_X3_REGS;
+    if (e && e[0] == 'g') g_stage = HDP_X3_GLDS;
   }
   return g_stage;
 }
-static bool use_x3(int r, int nseg) {
-  const int m = k4_math();
-  return m == HDP_MATH_X3 || m == HDP_MATH_H2 || (m == HDP_MATH_AUTO && 2 * r * nseg > 32);
+static K4Knobs k4_knobs() {
+  K4Knobs kn;
+  kn.math = k4_math();
+  kn.stage = x3_stage();
+  if (const char* e = getenv("HDP_K4_STORE")) kn.store_f32 = e[0] == 'f';
+  if (const char* e = getenv("HDP_K4_RND")) kn.rnd_x3 = e[0] == 'x';
+  if (const char* e = getenv("HDP_K4_DEFER")) {
+    kn.defer_set = true;
+    kn.defer = atoi(e);
+  }
+  if (const char* e = getenv("HDP_DELTA_POL")) kn.pol = atoi(e) & 15;
+  return kn;
+}
+static int k4_fail(const K4Error& e) {
+  set_error("%s", e.msg);
+  return e.code;
+}
+
+// One plan kernel per K4Choice.  Every instance of a family has the same launch bounds and LDS, so the
+// family's float32 MERGE instance (`occ`) answers the occupancy query for all of them.
+using K4Kernel = void (*)(const DeltaArgs*, const int64_t*, int, int64_t);
+struct K4Pick {
+  K4Kernel fn = nullptr;
+  int block = 0;
+  K4Kernel occ = nullptr;
+};
+template <int M, int D, bool R, int P = 0>
+static K4Kernel k4_tiled(int family) {  // the four families that share <MODE, DT, ROUND, POL>
+  switch (family) {
+    case K4_F32: return delta_group_kernel<M, D, R, P, MF32>;
+    case K4_X3_REGS: return delta_x3p_kernel<M, D, R, P>;
+    case K4_X3_GLDS: return delta_x3g_kernel<M, D, R, P>;
+    case K4_X3_WIDE: return delta_x3w_kernel<M, D, R, P>;
+  }
+  return nullptr;
+}
+static K4Kernel k4_kernel(const K4Choice& c) {  // c is valid (k4_choice_valid)
+  constexpr int ST = HDP_DW_STORE, MG = HDP_DW_MERGE, F = HDP_F32, B = HDP_BF16;
+  if (c.family == K4_H2) {
+    if (c.mode == ST) return delta_h2_kernel<ST, 0>;
+    if (c.dtype == B) {
+      if (c.def == 3) return c.round ? delta_h2_kernel<MG, 0, 3, B, true> : delta_h2_kernel<MG, 0, 3, B>;
+      return c.round ? delta_h2_kernel<MG, 0, 0, B, true> : delta_h2_kernel<MG, 0, 0, B>;
+    }
+    switch (c.def) {
+      case 0: return c.pol == 3 ? delta_h2_kernel<MG, 3> : delta_h2_kernel<MG, 0>;
+      case 2: return delta_h2_kernel<MG, 3, 2>;
+      case 4: return delta_h2_kernel<MG, 3, 4>;
+    }
+    return nullptr;
+  }
+  if (c.mode == ST) return c.round ? k4_tiled<ST, F, true>(c.family) : k4_tiled<ST, F, false>(c.family);
+  if (c.dtype == B) return c.round ? k4_tiled<MG, B, true>(c.family) : k4_tiled<MG, B, false>(c.family);
+  if (c.def == 1) return delta_x3w_kernel<MG, F, false, 3, 1>;
+  if (c.def == 2) return delta_x3w_kernel<MG, F, false, 3, 2>;
+  switch (c.pol) {
+    case 0: return k4_tiled<MG, F, false, 0>(c.family);
+    case 1: return k4_tiled<MG, F, false, 1>(c.family);
+    case 2: return k4_tiled<MG, F, false, 2>(c.family);
+    case 3: return k4_tiled<MG, F, false, 3>(c.family);
+    case 4: return k4_tiled<MG, F, false, 4>(c.family);
+    case 7: return k4_tiled<MG, F, false, 7>(c.family);
+    case 11: return k4_tiled<MG, F, false, 11>(c.family);
+    case 15: return k4_tiled<MG, F, false, 15>(c.family);
+  }
+  return nullptr;
+}
+static K4Pick pick_k4(const K4Choice& c) {
+  K4Pick k;
+  if (!k4_choice_valid(c)) return k;
+  k.fn = k4_kernel(c);
+  k.block = (c.family == K4_H2 || c.family == K4_X3_WIDE) ? 512 : 256;
+  // (the x3 regs / glds kernels share the f32 group kernel's launch bounds (256, 2) and are answered by it)
+  k.occ = c.family == K4_H2        ? delta_h2_kernel<HDP_DW_MERGE, 0>
+          : c.family == K4_X3_WIDE ? delta_x3w_kernel<HDP_DW_MERGE, HDP_F32, false, 0>
+                                   : delta_group_kernel<HDP_DW_MERGE, HDP_F32, false>;
+  return k;
 }
 
 }  // namespace hdp
@@ -2743,7 +2737,7 @@ extern "C" int hdp_delta_set_math(int math) {
 }
 
 extern "C" int hdp_delta_set_x3_stage(int stage) {
-  if (stage != X3_REGS && stage != X3_GLDS && stage != X3_WIDE) {  // -1: the valid returns are 0..2
+  if (stage != HDP_X3_REGS && stage != HDP_X3_GLDS && stage != HDP_X3_WIDE) {  // -1: the valid returns are 0..2
     set_error("hdp_delta_set_x3_stage: bad stage %d", stage);
     return -1;
   }
@@ -2757,10 +2751,10 @@ extern "C" int hdp_delta_gemm(int64_t out, int64_t in, int r, int nseg, const fl
                               int64_t factor_seg_stride, void* dst, int dst_dtype, int mode, int round_bf16,
                               void* stream) {
   DeltaArgs a;
-  const int rc = make_args("hdp_delta_gemm", out, in, r, nseg, dA, dB, delta_seg_stride, A, B, factor_seg_stride, dst,
-                           dst_dtype, mode, round_bf16, a);
-  if (rc != HDP_OK) return rc;
-  const int64_t nwg = args_tiles(a);
+  const K4Error e = k4_make_args("hdp_delta_gemm", out, in, r, nseg, dA, dB, delta_seg_stride, A, B,
+                                 factor_seg_stride, dst, dst_dtype, mode, round_bf16, a);
+  if (e.code != HDP_OK) return k4_fail(e);
+  const int64_t nwg = k4_args_tiles(a);
   HDP_CHECK_ARG(nwg < (1ll << 31), "hdp_delta_gemm: grid too large");
   hipStream_t st = as_stream(stream);
   dim3 grid((unsigned)nwg), block(256);
@@ -2768,13 +2762,13 @@ extern "C" int hdp_delta_gemm(int64_t out, int64_t in, int r, int nseg, const fl
   // reference's rank-by-rank sum only at the 1e-7 level); bf16 with round_bf16: the
   // rank-ordered running sum with bf16 rounding after every segment, as hp:389-392 does.
   const bool rnd = round_bf16 != 0;
-  const bool x3 = use_x3(r, nseg);
+  const bool x3 = k4_use_x3(k4_math(), r, nseg);
 #define HDP_LAUNCH(M, D, R)                                                                 \
   do {                                                                                      \
     if (x3) hipLaunchKernelGGL((delta_gemm_kernel<M, D, R, MX3>), grid, block, 0, st, a); \
     else hipLaunchKernelGGL((delta_gemm_kernel<M, D, R, MF32>), grid, block, 0, st, a);   \
   } while (0)
-  KTimer kt(nseg == 1 ? K_DELTA : K_DELTA_MULTI, st, args_bytes(a, mode, dst_dtype), args_flops(a));
+  KTimer kt(nseg == 1 ? K_DELTA : K_DELTA_MULTI, st, k4_args_bytes(a, mode, dst_dtype), k4_args_flops(a));
   if (mode == HDP_DW_STORE) {
     if (rnd) HDP_LAUNCH(HDP_DW_STORE, HDP_F32, true);
     else HDP_LAUNCH(HDP_DW_STORE, HDP_F32, false);
@@ -2791,45 +2785,78 @@ extern "C" int hdp_delta_gemm(int64_t out, int64_t in, int r, int nseg, const fl
 
 // ---- grouped plans ----------------------------------------------------------------------
 struct hdp_delta_plan_s {
-  DeltaArgs* d_items = nullptr;   // device copies of the descriptors
-  int64_t* d_start = nullptr;     // device tile prefix (n + 1)
+  K4Plan k;     // the host plan: choice, totals, accounting
+  K4Pick pick;  // its kernel
   int n = 0;
-  int64_t total = 0;
-  int mode = 0, dtype = 0, round = 0;
   int grid = 0;
-  int multiseg = 0;
-  int pol = 3;  // float32 MERGE cache policy (HDP_DELTA_POL: bit 0 nt stores, bit 1 nt W loads)
-  int x3 = 0;   // bf16x3 split math (decided at creation from the largest K of the items)
-  int stage = 0;  // x3: X3_REGS / X3_GLDS / X3_WIDE (fixes the tile geometry of tile_start)
-  int def = 0;    // deferred W merge: X3WDefer 1 / 2 (float32 MERGE), 3 = bf16 H2 MERGE (delta_h2_kernel)
-  int h2 = 0;     // fp16x2 scaled split (delta_h2_kernel; float32 MERGE / STORE plans)
-  float* d_ktab = nullptr;  // h2: per-item scale tables
-  int* d_sstart = nullptr;  // h2: k4_h2_scale_kernel workgroup prefix per item
-  int sblocks = 0;
-  __bf16* d_img = nullptr;         // x3: packed operand panels of every item (MX3P)
-  int64_t* d_pack_start = nullptr; // x3: k4_pack_kernel thread-space prefix (256-aligned)
-  int64_t* d_ap_start = nullptr;   // fused: k4_h2_adam_pack_kernel thread-space prefix (256-aligned)
-  int64_t ap_total = 0;
-  int64_t pack_total = 0;
-  double bytes = 0.0, flops = 0.0;
-  int fused = 0;        // h2 single-segment MERGE: hdp_delta_plan_run_adam applies
-  double pack_bytes = 0.0;  // x3 / H2 operand preparation: factors read by the scale pass (H2) and the pack,
-                            // panels written (24 B per (row or column, k-slot) for H2, 20 B for x3)
-  double adam_bytes = 0.0;  // fused Adam + pack: g, m, v read, m, v, delta, g written (28 B per entry),
-                            // + A read and 8 B of R panel per A entry, 4 B of L panel per B entry
-  int const_done = 0;   // fused: constant maxima and the constant panel halves written
-  int* d_gate = nullptr;
+  DeltaArgs* d_items = nullptr;     // device copies of the descriptors
+  int64_t* d_start = nullptr;       // device tile prefix (n + 1)
+  k4_img_t* d_img = nullptr;        // x3: packed operand panels of every item (MX3P; fp16x2 under H2)
+  int64_t* d_pack_start = nullptr;  // x3: pack kernel thread-space prefix
+  float* d_ktab = nullptr;          // h2: per-item scale tables
+  int* d_sstart = nullptr;          // h2: k4_h2_scale_kernel workgroup prefix per item
+  int64_t* d_ap_start = nullptr;    // fused: k4_h2_adam_pack_kernel thread-space prefix
+  int* d_gate = nullptr;            // fused: the fallback's gate word
+  int const_done = 0;               // fused: constant maxima and the constant panel halves written
 };
 
-template <class K>
-static int plan_grid(K kernel, int threads, int64_t total, int& grid) {
+static int plan_grid(const K4Pick& k, int64_t total, int& grid) {
   int dev = 0, cus = 0, per_cu = 0;
   HDP_CHECK_HIP(hipGetDevice(&dev));
   HDP_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  HDP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0));
+  HDP_CHECK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.occ, k.block, 0));
   const int64_t resident = (int64_t)std::max(per_cu, 1) * std::max(cus, 1);
   grid = (int)std::min<int64_t>(resident, total);
   if (grid >= 8) grid -= grid % 8;  // the XCD-contiguous schedule deals G / 8 workgroups per XCD
+  return HDP_OK;
+}
+
+template <class T>
+static bool k4_upload(T** dev, const std::vector<T>& host) {
+  return hipMalloc(dev, sizeof(T) * host.size()) == hipSuccess &&
+         hipMemcpy(*dev, host.data(), sizeof(T) * host.size(), hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// knobs -> k4_plan -> allocate -> patch limg / rimg / ktab from the planned offsets -> upload
+static int plan_build(hdp_delta_plan p, const hdp_delta_item* items, int n, int dst_dtype, int mode, int round_bf16) {
+  K4Plan& k = p->k;
+  const K4Error e = k4_plan(items, n, dst_dtype, mode, round_bf16, k4_knobs(), k);
+  if (e.code != HDP_OK) return k4_fail(e);
+  p->n = n;
+  p->pick = pick_k4(k.choice);
+  HDP_CHECK_ARG(p->pick.fn, "hdp_delta_plan_create: no kernel for the planned choice");
+  const int rc = plan_grid(p->pick, k.total, p->grid);
+  if (rc != HDP_OK) return rc;
+  if (k.x3()) {
+    if (hipMalloc(&p->d_img, sizeof(k4_img_t) * k.img_elems) != hipSuccess || !k4_upload(&p->d_pack_start, k.pstart)) {
+      set_error("hdp_delta_plan_create: packed-panel workspace allocation failed (%lld bytes)",
+                (long long)(sizeof(k4_img_t) * k.img_elems));
+      return HDP_EHIP;
+    }
+    if (k.h2() && (hipMalloc(&p->d_ktab, sizeof(float) * k.ktab_floats) != hipSuccess ||
+                   hipMemset(p->d_ktab, 0, sizeof(float) * k.ktab_floats) != hipSuccess ||
+                   !k4_upload(&p->d_sstart, k.sstart))) {
+      set_error("hdp_delta_plan_create: scale-table allocation failed");
+      return HDP_EHIP;
+    }
+    for (int i = 0; i < n; ++i) {
+      k.args[i].limg = p->d_img + k.off[i].limg;
+      k.args[i].rimg = p->d_img + k.off[i].rimg;
+      if (k.h2()) k.args[i].ktab = p->d_ktab + k.off[i].ktab;
+    }
+  }
+  if (k.fused && !k4_upload(&p->d_ap_start, k.apst)) {
+    set_error("hdp_delta_plan_create: fused-Adam table allocation failed");
+    return HDP_EHIP;
+  }
+  if (k.fused && (hipMalloc(&p->d_gate, 256) != hipSuccess || hipMemset(p->d_gate, 0, 256) != hipSuccess)) {
+    set_error("hdp_delta_plan_create: gate allocation failed");
+    return HDP_EHIP;
+  }
+  if (!k4_upload(&p->d_items, k.args) || !k4_upload(&p->d_start, k.start)) {
+    set_error("hdp_delta_plan_create: device table allocation/copy failed");
+    return HDP_EHIP;
+  }
   return HDP_OK;
 }
 
@@ -2837,177 +2864,8 @@ extern "C" int hdp_delta_plan_create(const hdp_delta_item* items, int n, int dst
                                      hdp_delta_plan* plan) {
   HDP_CHECK_ARG(plan && items && n > 0, "hdp_delta_plan_create: need a plan pointer and n > 0 items");
   *plan = nullptr;
-  std::vector<DeltaArgs> host(n);
-  std::vector<int64_t> start(n + 1, 0);
-  double bytes = 0.0, flops = 0.0;
-  int multiseg = 0, kmax_r = 0, kmax_seg = 1;
-  for (int i = 0; i < n; ++i) {
-    const hdp_delta_item& it = items[i];
-    const int rc = make_args("hdp_delta_plan_create", it.out, it.in, it.r, it.nseg, it.dA, it.dB, it.delta_seg_stride,
-                             it.A, it.B, it.factor_seg_stride, it.dst, dst_dtype, mode, round_bf16, host[i]);
-    if (rc != HDP_OK) return rc;
-    bytes += args_bytes(host[i], mode, dst_dtype);
-    flops += args_flops(host[i]);
-    multiseg |= it.nseg > 1;
-    if (2 * it.r * it.nseg > 2 * kmax_r * kmax_seg) {
-      kmax_r = it.r;
-      kmax_seg = it.nseg;
-    }
-  }
-  // float32 STORE plans at K = 32 (Wn = 1, r = 16): the exact f32 MFMA form is MFMA-bound there (half the
-  // bytes of a MERGE behind the same 64-cycle f32 MFMAs), so AUTO takes H2 from K = 32 on; env
-  // HDP_K4_STORE=f32 keeps the f32 form
-  bool store_h2 = mode == HDP_DW_STORE && !round_bf16 && k4_math() == HDP_MATH_AUTO && 2 * kmax_r * kmax_seg >= 32;
-  if (const char* e = getenv("HDP_K4_STORE")) store_h2 = store_h2 && e[0] != 'f';
-  const bool x3 = use_x3(kmax_r, kmax_seg) || store_h2;
-  // a bf16 MERGE of single-segment items (Wn = 1): the ROUND form's dW = bf16(0 - bracket) added as
-  // bf16(W + bf16(dW)) is bit-identical to the plain form, whose epilogue adds bf16(-acc) -- so it
-  // runs without the running sum (and on the wide x3 kernel, which the ROUND form's registers spill)
-  if (round_bf16 && mode == HDP_DW_MERGE && dst_dtype == HDP_BF16 && !multiseg) round_bf16 = 0;
-  // the wide x3 kernel's bf16 ROUND merge (running sum + accumulators + bf16 W) spills: X3G there
-  int stage = x3 ? x3_stage() : X3_REGS;
-  // H2 (AUTO or HDP_MATH_H2) for float32 results and for bf16 merges without per-rank rounding
-  // (single-segment plans, see above); bf16 ROUND merges keep bf16x3
-  // bf16 ROUND merges (Wn > 1) run on H2 too when every segment ends on a 32-k chunk boundary
-  // (ceil(r / 8) even, i.e. r % 16 == 0 for the BASELINE configs): per-segment bf16 folds in the
-  // kernel (RND); HDP_K4_RND=x3 keeps them on bf16x3
-  bool rnd_h2 = round_bf16 && mode == HDP_DW_MERGE && dst_dtype == HDP_BF16;
-  for (int i = 0; i < n && rnd_h2; ++i) rnd_h2 = (((host[i].r + MX3::kSteps - 1) / MX3::kSteps) & 1) == 0;
-  if (const char* e = getenv("HDP_K4_RND")) rnd_h2 = rnd_h2 && e[0] != 'x';
-  const bool h2 = x3 && (k4_math() == HDP_MATH_AUTO || k4_math() == HDP_MATH_H2) && (!round_bf16 || rnd_h2);
-  if (h2) stage = X3_WIDE;  // the same 256 x 128 tile geometry
-  else if (stage == X3_WIDE && mode == HDP_DW_MERGE && dst_dtype == HDP_BF16 && round_bf16) stage = X3_GLDS;
-  const int tr = (x3 && stage == X3_WIDE) ? 2 * kDT : kDT;
-  for (int i = 0; i < n; ++i) start[i + 1] = start[i] + args_tiles(host[i], tr);
   hdp_delta_plan p = new hdp_delta_plan_s;
-  p->n = n;
-  p->total = start[n];
-  p->mode = mode;
-  p->dtype = dst_dtype;
-  p->round = round_bf16 != 0;
-  p->multiseg = multiseg;
-  p->bytes = bytes;
-  p->flops = flops;
-  if (const char* e = getenv("HDP_DELTA_POL")) p->pol = atoi(e) & 15;
-  p->x3 = x3;
-  p->stage = stage;
-  p->h2 = h2;
-  if (h2 && mode == HDP_DW_MERGE && dst_dtype == HDP_F32) {  // H2 chunks are 32 k: X3WDefer<2> needs min_chunks
-    int64_t nch_min = INT64_MAX;
-    for (int i = 0; i < n; ++i)
-      nch_min = std::min<int64_t>(nch_min, (host[i].nseg * ((host[i].r + MX3::kSteps - 1) / MX3::kSteps) + 1) / 2);
-    // X3WDefer<4> (W loads two chunks ahead) where every tile has >= 7 chunks: LLaMA-2-7B shapes at Wn = 8,
-    // 4 layers 2.415 -> 2.341 ms (tools/delta_bench.py --pol 3, r04)
-    int want = 4;
-    if (const char* e = getenv("HDP_K4_DEFER")) want = atoi(e);
-    if (want == 4 && nch_min < x3w_defer_min_chunks<4>()) want = 2;
-    p->def = (want != 0 && nch_min >= x3w_defer_min_chunks<2>()) ? (want == 4 ? 4 : 2) : 0;
-  }
-  if (h2 && mode == HDP_DW_MERGE && dst_dtype == HDP_BF16) {  // deferred bf16 merge: every tile >= 4 chunks
-    // (Mistral-7B r = 64, 8 layers: 3.28 -> 3.15 ms per run, tools/delta_bench.py, r03)
-    int64_t nch_min = INT64_MAX;
-    for (int i = 0; i < n; ++i)
-      nch_min = std::min<int64_t>(nch_min, (host[i].nseg * ((host[i].r + MX3::kSteps - 1) / MX3::kSteps) + 1) / 2);
-    int want = 3;
-    if (const char* e = getenv("HDP_K4_DEFER")) want = atoi(e) == 0 ? 0 : 3;
-    p->def = (want == 3 && nch_min >= 4) ? 3 : 0;
-  }
-  if (x3 && !h2 && stage == X3_WIDE && mode == HDP_DW_MERGE && dst_dtype == HDP_F32 && !round_bf16) {
-    // the deferred merge needs every tile's chunk count >= the variant's min_chunks
-    int64_t nch_min = host[0].nseg * ((host[0].r + MX3::kSteps - 1) / MX3::kSteps);
-    for (int i = 1; i < n; ++i)
-      nch_min = std::min<int64_t>(nch_min, host[i].nseg * ((host[i].r + MX3::kSteps - 1) / MX3::kSteps));
-    int want = 0;  // measured slower so far (register pressure): opt-in
-    if (const char* e = getenv("HDP_K4_DEFER")) want = atoi(e);
-    if (want == 1 && nch_min < x3w_defer_min_chunks<1>()) want = 2;
-    if (want == 2 && nch_min < x3w_defer_min_chunks<2>()) want = 0;
-    p->def = (want == 1 || want == 2) ? want : 0;
-  }
-  std::vector<int64_t> pstart(n + 1, 0);
-  int64_t img_elems = 0;
-  std::vector<int64_t> img_off(n, 0);
-  // H2: panels of 16 k per (chunk, block), the chunk count padded to even; scale tables
-  std::vector<int64_t> ktab_off(n, 0);
-  std::vector<int> sstart(n + 1, 0);
-  int64_t ktab_floats = 0;
-  auto img_chunks = [&](const DeltaArgs& a) {
-    const int64_t nch = (int64_t)a.nseg * ((a.r + MX3::kSteps - 1) / MX3::kSteps);
-    return h2 ? (nch + 1) / 2 * 2 : nch;
-  };
-  const int64_t panel = h2 ? kPanelH : kPanel;
-  if (p->x3) {
-    for (int i = 0; i < n; ++i) {
-      const DeltaArgs& a = host[i];
-      const int64_t nch = img_chunks(a);
-      const int64_t nRB = (a.out + kDT - 1) / kDT, nCB = (a.in + kDT - 1) / kDT;
-      img_off[i] = img_elems;
-      img_elems += nch * (nRB + nCB) * panel;
-      const int64_t th = (h2 ? nch / 2 : nch) * (nRB + nCB) * kDT;  // H2: a thread per pair of chunks
-      pstart[i + 1] = pstart[i] + (th + 255) / 256 * 256;
-      ktab_off[i] = ktab_floats;
-      ktab_floats += (h2_tab_floats(a.out, a.in, a.r, a.nseg) + 63) / 64 * 64;
-      sstart[i + 1] = sstart[i] + a.nseg * (int)((a.out + 255) / 256 + (a.in + 255) / 256);
-    }
-    p->pack_total = pstart[n];
-    p->sblocks = sstart[n];
-    for (int i = 0; i < n; ++i)
-      p->pack_bytes += (h2 ? 24.0 : 20.0) * host[i].r * host[i].nseg * (double)(host[i].out + host[i].in);
-  }
-  int rc = HDP_OK;
-  // every instance of a kernel has the same launch bounds and LDS: the f32 MERGE instance
-  // stands for all of them in the occupancy query
-  if (h2) rc = plan_grid(delta_h2_kernel<HDP_DW_MERGE, 0>, 512, p->total, p->grid);
-  else if (x3 && stage == X3_WIDE) rc = plan_grid(delta_x3w_kernel<HDP_DW_MERGE, HDP_F32, false, 0>, 512, p->total, p->grid);
-  else rc = plan_grid(delta_group_kernel<HDP_DW_MERGE, HDP_F32, false>, 256, p->total, p->grid);
-  if (rc == HDP_OK && p->x3) {
-    if (hipMalloc(&p->d_img, sizeof(__bf16) * img_elems) != hipSuccess ||
-        hipMalloc(&p->d_pack_start, sizeof(int64_t) * (n + 1)) != hipSuccess ||
-        hipMemcpy(p->d_pack_start, pstart.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) != hipSuccess) {
-      set_error("hdp_delta_plan_create: packed-panel workspace allocation failed (%lld bytes)",
-                (long long)(sizeof(__bf16) * img_elems));
-      rc = HDP_EHIP;
-    } else if (h2 && (hipMalloc(&p->d_ktab, sizeof(float) * ktab_floats) != hipSuccess ||
-                      hipMemset(p->d_ktab, 0, sizeof(float) * ktab_floats) != hipSuccess ||
-                      hipMalloc(&p->d_sstart, sizeof(int) * (n + 1)) != hipSuccess ||
-                      hipMemcpy(p->d_sstart, sstart.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice) !=
-                          hipSuccess)) {
-      set_error("hdp_delta_plan_create: scale-table allocation failed");
-      rc = HDP_EHIP;
-    } else {
-      for (int i = 0; i < n; ++i) {
-        const DeltaArgs& a = host[i];
-        const int64_t nch = img_chunks(a);
-        host[i].limg = p->d_img + img_off[i];
-        host[i].rimg = p->d_img + img_off[i] + nch * ((a.out + kDT - 1) / kDT) * panel;
-        if (h2) host[i].ktab = p->d_ktab + ktab_off[i];
-      }
-    }
-  }
-  p->fused = h2 && !multiseg && mode == HDP_DW_MERGE;
-  std::vector<int64_t> apst(n + 1, 0);
-  for (int i = 0; i < n && p->fused; ++i) {
-    p->adam_bytes += (double)host[i].r * ((28.0 + 4.0) * host[i].out + (28.0 + 4.0 + 8.0) * host[i].in);
-    apst[i + 1] = apst[i] + (h2_ap_threads(host[i].out, host[i].in, host[i].r) + 255) / 256 * 256;
-  }
-  p->ap_total = apst[n];
-  if (rc == HDP_OK && p->fused &&
-      (hipMalloc(&p->d_ap_start, sizeof(int64_t) * (n + 1)) != hipSuccess ||
-       hipMemcpy(p->d_ap_start, apst.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) != hipSuccess)) {
-    set_error("hdp_delta_plan_create: fused-Adam table allocation failed");
-    rc = HDP_EHIP;
-  }
-  if (rc == HDP_OK && p->fused && (hipMalloc(&p->d_gate, 256) != hipSuccess || hipMemset(p->d_gate, 0, 256) != hipSuccess)) {
-    set_error("hdp_delta_plan_create: gate allocation failed");
-    rc = HDP_EHIP;
-  }
-  if (rc == HDP_OK && (hipMalloc(&p->d_items, sizeof(DeltaArgs) * n) != hipSuccess ||
-                       hipMalloc(&p->d_start, sizeof(int64_t) * (n + 1)) != hipSuccess ||
-                       hipMemcpy(p->d_items, host.data(), sizeof(DeltaArgs) * n, hipMemcpyHostToDevice) != hipSuccess ||
-                       hipMemcpy(p->d_start, start.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) !=
-                           hipSuccess)) {
-    set_error("hdp_delta_plan_create: device table allocation/copy failed");
-    rc = HDP_EHIP;
-  }
+  const int rc = plan_build(p, items, n, dst_dtype, mode, round_bf16);
   if (rc != HDP_OK) {
     hdp_delta_plan_destroy(p);
     return rc;
@@ -3016,14 +2874,42 @@ extern "C" int hdp_delta_plan_create(const hdp_delta_item* items, int n, int dst
   return HDP_OK;
 }
 
-static int plan_launch(hdp_delta_plan p, hipStream_t st, bool pack);
+// H2 operand preparation from the live factors: the scale table, then the scaled fp16 panels.  gate: the
+// fused path's fallback passes its word and the three kernels run only when it is set; null = always
+static void h2_pack_live(hdp_delta_plan p, hipStream_t st, const int* gate) {
+  hipLaunchKernelGGL(k4_h2_scale_kernel, dim3((unsigned)p->k.sblocks), dim3(256), 0, st, p->d_items, p->d_sstart, p->n,
+                     gate);
+  hipLaunchKernelGGL(k4_h2_fin_kernel, dim3((unsigned)p->n), dim3(256), 0, st, p->d_items, gate);
+  hipLaunchKernelGGL(k4_h2_pack_kernel, dim3((unsigned)(p->k.pack_total / 256)), dim3(256), 0, st, p->d_items,
+                     p->d_pack_start, p->n, gate);
+}
+
+static int plan_launch(hdp_delta_plan p, hipStream_t st, bool pack) {
+  const K4Plan& k = p->k;
+  if (k.x3() && pack) {  // pack the operand panels first (same stream: K4 below reads them)
+    KTimer kp(K_DELTA_PACK, st, k.pack_bytes);
+    if (k.h2()) {
+      p->const_done = 0;  // (a later fused run re-packs the constant halves with its own scale rule)
+      h2_pack_live(p, st, nullptr);
+    } else {
+      hipLaunchKernelGGL(k4_pack_kernel, dim3((unsigned)(k.pack_total / 256)), dim3(256), 0, st, p->d_items,
+                         p->d_pack_start, p->n);
+    }
+  }
+  HDP_CHECK_LAUNCH();
+  KTimer kt(k.multiseg ? K_DELTA_MULTI : K_DELTA, st, k.bytes, k.flops);
+  hipLaunchKernelGGL(p->pick.fn, dim3((unsigned)p->grid), dim3((unsigned)p->pick.block), 0, st, p->d_items, p->d_start,
+                     p->n, k.total);
+  HDP_CHECK_LAUNCH();
+  return HDP_OK;
+}
 
 extern "C" int hdp_delta_plan_run(hdp_delta_plan p, void* stream) {
   HDP_CHECK_ARG(p && p->d_items && p->grid > 0, "hdp_delta_plan_run: invalid plan");
   return plan_launch(p, as_stream(stream), true);
 }
 
-extern "C" int hdp_delta_plan_fused_adam(hdp_delta_plan p) { return p ? p->fused : 0; }
+extern "C" int hdp_delta_plan_fused_adam(hdp_delta_plan p) { return p ? p->k.fused : 0; }
 
 extern "C" int hdp_delta_plan_invalidate(hdp_delta_plan p) {
   HDP_CHECK_ARG(p, "hdp_delta_plan_invalidate: null plan");
@@ -3036,7 +2922,7 @@ static int plan_run_adam(hdp_delta_plan p, float* grad, float* m, float* v, floa
                          float bc2, float lr, float eps, float delta_bound, int zero_grad,
                          const hdp_clip_state* clip, void* stream) {
   HDP_CHECK_ARG(p && p->d_items && p->grid > 0, "hdp_delta_plan_run_adam: invalid plan");
-  HDP_CHECK_ARG(p->fused, "hdp_delta_plan_run_adam: the plan has no fused Adam (single-segment H2 merge plans only)");
+  HDP_CHECK_ARG(p->k.fused, "hdp_delta_plan_run_adam: the plan has no fused Adam (single-segment H2 merge plans only)");
   HDP_CHECK_ARG(grad && m && v && delta, "hdp_delta_plan_run_adam: null arena pointer");
   HDP_CHECK_ARG(bc1 != 0.f && bc2 != 0.f, "hdp_delta_plan_run_adam: bias correction is zero (t == 0?)");
   HDP_CHECK_ARG(delta_bound >= 0.f, "hdp_delta_plan_run_adam: negative delta bound");
@@ -3045,11 +2931,7 @@ static int plan_run_adam(hdp_delta_plan p, float* grad, float* m, float* v, floa
     KTimer kp(K_DELTA_PACK, st, 0.0);
     if (!p->const_done) {  // once: constant maxima, and every panel (the constant L half 1 = B included)
       hipLaunchKernelGGL(k4_h2_cmax_kernel, dim3((unsigned)p->n, 2), dim3(256), 0, st, p->d_items);
-      hipLaunchKernelGGL(k4_h2_scale_kernel, dim3((unsigned)p->sblocks), dim3(256), 0, st, p->d_items, p->d_sstart,
-                         p->n, (const int*)nullptr);
-      hipLaunchKernelGGL(k4_h2_fin_kernel, dim3((unsigned)p->n), dim3(256), 0, st, p->d_items, (const int*)nullptr);
-      hipLaunchKernelGGL(k4_h2_pack_kernel, dim3((unsigned)(p->pack_total / 256)), dim3(256), 0, st, p->d_items,
-                         p->d_pack_start, p->n, (const int*)nullptr);
+      h2_pack_live(p, st, nullptr);
       HDP_CHECK_LAUNCH();
       p->const_done = 1;
     }
@@ -3057,7 +2939,7 @@ static int plan_run_adam(hdp_delta_plan p, float* grad, float* m, float* v, floa
   }
   HDP_CHECK_LAUNCH();
   {
-    KTimer ka(K_ADAM, st, p->adam_bytes);
+    KTimer ka(K_ADAM, st, p->k.adam_bytes);
     AdamPackArgs ap;
     ap.gate = p->d_gate;
     ap.D = delta_bound;
@@ -3069,22 +2951,17 @@ static int plan_run_adam(hdp_delta_plan p, float* grad, float* m, float* v, floa
     ap.clip = clip;
     ap.s = AdamScalars{grad_scale, beta1, one_minus_beta1, beta2, one_minus_beta2, bc1, bc2, lr, eps};
     ap.zero = zero_grad ? 1 : 0;
+    const dim3 apgrid((unsigned)(p->k.ap_total / 256));
     if (clip)
-      hipLaunchKernelGGL(k4_h2_adam_pack_kernel<true>, dim3((unsigned)(p->ap_total / 256)), dim3(256), 0, st,
-                         p->d_items, p->d_ap_start, p->n, ap);
+      hipLaunchKernelGGL(k4_h2_adam_pack_kernel<true>, apgrid, dim3(256), 0, st, p->d_items, p->d_ap_start, p->n, ap);
     else
-      hipLaunchKernelGGL(k4_h2_adam_pack_kernel<false>, dim3((unsigned)(p->ap_total / 256)), dim3(256), 0, st,
-                         p->d_items, p->d_ap_start, p->n, ap);
+      hipLaunchKernelGGL(k4_h2_adam_pack_kernel<false>, apgrid, dim3(256), 0, st, p->d_items, p->d_ap_start, p->n, ap);
   }
   HDP_CHECK_LAUNCH();
   {  // fallback: only if a delta exceeded D (moments not from this Adam sequence) -- then the gated
      // passes rebuild the scales and every panel from the live deltas; otherwise three empty launches
     KTimer kp(K_DELTA_PACK, st, 0.0);
-    hipLaunchKernelGGL(k4_h2_scale_kernel, dim3((unsigned)p->sblocks), dim3(256), 0, st, p->d_items, p->d_sstart, p->n,
-                       (const int*)p->d_gate);
-    hipLaunchKernelGGL(k4_h2_fin_kernel, dim3((unsigned)p->n), dim3(256), 0, st, p->d_items, (const int*)p->d_gate);
-    hipLaunchKernelGGL(k4_h2_pack_kernel, dim3((unsigned)(p->pack_total / 256)), dim3(256), 0, st, p->d_items,
-                       p->d_pack_start, p->n, (const int*)p->d_gate);
+    h2_pack_live(p, st, p->d_gate);
   }
   HDP_CHECK_LAUNCH();
   return plan_launch(p, st, false);
@@ -3114,113 +2991,14 @@ extern "C" int hdp_delta_plan_fused_fallback(hdp_delta_plan p, int* taken) {
   return HDP_OK;
 }
 
-static int plan_launch(hdp_delta_plan p, hipStream_t st, bool pack) {
-  DeltaGroup g{p->d_items, p->d_start, p->n, p->total};
-  dim3 grid((unsigned)p->grid), block(256), wblock(512);
-#define HDP_LAUNCH_K(M, D, R, P)                                                                            \
-  do {                                                                                                      \
-    if (p->x3 && p->stage == X3_WIDE)                                                                       \
-      hipLaunchKernelGGL((delta_x3w_kernel<M, D, R, P>), grid, wblock, 0, st, g.items, g.tile_start, g.n,     \
-                         g.total);                                                                          \
-    else if (p->x3 && p->stage == X3_GLDS)                                                                  \
-      hipLaunchKernelGGL((delta_x3g_kernel<M, D, R, P>), grid, block, 0, st, g.items, g.tile_start, g.n,      \
-                         g.total);                                                                          \
-    else if (p->x3)                                                                                         \
-      hipLaunchKernelGGL((delta_x3p_kernel<M, D, R, P>), grid, block, 0, st, g.items, g.tile_start, g.n,      \
-                         g.total);                                                                          \
-    else                                                                                                    \
-      hipLaunchKernelGGL((delta_group_kernel<M, D, R, P, MF32>), grid, block, 0, st, g.items, g.tile_start,     \
-                         g.n, g.total);                                                                     \
-  } while (0)
-#define HDP_LAUNCH(M, D, R) HDP_LAUNCH_K(M, D, R, 0)
-#define HDP_LAUNCH_P(M, D, P) HDP_LAUNCH_K(M, D, false, P)
-  if (p->x3 && pack) {  // pack the operand panels first (same stream: K4 below reads them)
-    KTimer kp(K_DELTA_PACK, st, p->pack_bytes);
-    if (p->h2) {  // the scale table from the live factors, then the scaled fp16 panels
-      p->const_done = 0;  // (a later fused run re-packs the constant halves with its own scale rule)
-      hipLaunchKernelGGL(k4_h2_scale_kernel, dim3((unsigned)p->sblocks), dim3(256), 0, st, p->d_items, p->d_sstart,
-                         p->n, (const int*)nullptr);
-      hipLaunchKernelGGL(k4_h2_fin_kernel, dim3((unsigned)p->n), dim3(256), 0, st, p->d_items, (const int*)nullptr);
-      hipLaunchKernelGGL(k4_h2_pack_kernel, dim3((unsigned)(p->pack_total / 256)), dim3(256), 0, st, p->d_items,
-                         p->d_pack_start, p->n, (const int*)nullptr);
-    } else {
-      hipLaunchKernelGGL(k4_pack_kernel, dim3((unsigned)(p->pack_total / 256)), dim3(256), 0, st, p->d_items,
-                         p->d_pack_start, p->n);
-    }
-  }
-  HDP_CHECK_LAUNCH();
-  if (p->h2) {
-    KTimer kt(p->multiseg ? K_DELTA_MULTI : K_DELTA, st, p->bytes, p->flops);
-    if (p->mode == HDP_DW_STORE)
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_STORE, 0>), grid, wblock, 0, st, g.items, g.tile_start, g.n, g.total);
-    else if (p->dtype == HDP_BF16 && p->round && p->def == 3)
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_MERGE, 0, 3, HDP_BF16, true>), grid, wblock, 0, st, g.items,
-                         g.tile_start, g.n, g.total);
-    else if (p->dtype == HDP_BF16 && p->round)
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_MERGE, 0, 0, HDP_BF16, true>), grid, wblock, 0, st, g.items,
-                         g.tile_start, g.n, g.total);
-    else if (p->dtype == HDP_BF16 && p->def == 3)
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_MERGE, 0, 3, HDP_BF16>), grid, wblock, 0, st, g.items, g.tile_start,
-                         g.n, g.total);
-    else if (p->dtype == HDP_BF16)
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_MERGE, 0, 0, HDP_BF16>), grid, wblock, 0, st, g.items, g.tile_start,
-                         g.n, g.total);
-    else if (p->pol == 3 && p->def == 2)
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_MERGE, 3, 2>), grid, wblock, 0, st, g.items, g.tile_start, g.n,
-                         g.total);
-    else if (p->pol == 3 && p->def == 4)
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_MERGE, 3, 4>), grid, wblock, 0, st, g.items, g.tile_start, g.n,
-                         g.total);
-    else if (p->pol == 3)
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_MERGE, 3>), grid, wblock, 0, st, g.items, g.tile_start, g.n, g.total);
-    else
-      hipLaunchKernelGGL((delta_h2_kernel<HDP_DW_MERGE, 0>), grid, wblock, 0, st, g.items, g.tile_start, g.n, g.total);
-    HDP_CHECK_LAUNCH();
-    return HDP_OK;
-  }
-  KTimer kt(p->multiseg ? K_DELTA_MULTI : K_DELTA, st, p->bytes, p->flops);
-  if (p->mode == HDP_DW_STORE) {
-    if (p->round) HDP_LAUNCH(HDP_DW_STORE, HDP_F32, true);
-    else HDP_LAUNCH(HDP_DW_STORE, HDP_F32, false);
-  } else if (p->dtype == HDP_F32) {
-    switch (p->pol) {
-      case 1: HDP_LAUNCH_P(HDP_DW_MERGE, HDP_F32, 1); break;
-      case 2: HDP_LAUNCH_P(HDP_DW_MERGE, HDP_F32, 2); break;
-      case 3:
-        if (p->x3 && p->stage == X3_WIDE && p->def == 1)
-          hipLaunchKernelGGL((delta_x3w_kernel<HDP_DW_MERGE, HDP_F32, false, 3, 1>), grid, wblock, 0, st, g.items,
-                             g.tile_start, g.n, g.total);
-        else if (p->x3 && p->stage == X3_WIDE && p->def == 2)
-          hipLaunchKernelGGL((delta_x3w_kernel<HDP_DW_MERGE, HDP_F32, false, 3, 2>), grid, wblock, 0, st, g.items,
-                             g.tile_start, g.n, g.total);
-        else
-          HDP_LAUNCH_P(HDP_DW_MERGE, HDP_F32, 3);
-        break;
-      case 7: HDP_LAUNCH_P(HDP_DW_MERGE, HDP_F32, 7); break;
-      case 11: HDP_LAUNCH_P(HDP_DW_MERGE, HDP_F32, 11); break;
-      case 15: HDP_LAUNCH_P(HDP_DW_MERGE, HDP_F32, 15); break;
-      case 4: HDP_LAUNCH_P(HDP_DW_MERGE, HDP_F32, 4); break;
-      default: HDP_LAUNCH(HDP_DW_MERGE, HDP_F32, false);
-    }
-  } else {
-    if (p->round) HDP_LAUNCH(HDP_DW_MERGE, HDP_BF16, true);
-    else HDP_LAUNCH(HDP_DW_MERGE, HDP_BF16, false);
-  }
-#undef HDP_LAUNCH
-#undef HDP_LAUNCH_P
-#undef HDP_LAUNCH_K
-  HDP_CHECK_LAUNCH();
-  return HDP_OK;
-}
-
 extern "C" int hdp_delta_plan_math(hdp_delta_plan p) {
   if (!p) return -1;
-  return p->h2 ? HDP_MATH_H2 : p->x3 ? HDP_MATH_X3 : HDP_MATH_F32;
+  return p->k.h2() ? HDP_MATH_H2 : p->k.x3() ? HDP_MATH_X3 : HDP_MATH_F32;
 }
 
 extern "C" int hdp_delta_plan_tiles(hdp_delta_plan p, int64_t* tiles, int* grid) {
   HDP_CHECK_ARG(p, "hdp_delta_plan_tiles: null plan");
-  if (tiles) *tiles = p->total;
+  if (tiles) *tiles = p->k.total;
   if (grid) *grid = p->grid;
   return HDP_OK;
 }
