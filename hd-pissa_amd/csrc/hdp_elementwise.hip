@@ -5,6 +5,7 @@
 //   merge bf16 W:  8 B/element (read W 2, read dW 4, write W 2)
 //   adam        : 24 B/element (read g, m, v; write m, v, delta) (+4 with zero_grad)
 #include "hdp_common.h"
+#include "hdp_sr.h"
 
 namespace hdp {
 
@@ -301,6 +302,96 @@ __global__ void merge_scalar_kernel(void* W, int dt, const float* dW, int64_t be
 }
 
 // ---------------------------------------------------------------------------------------
+// Stochastic-rounding merge (hdp_merge_group_sr; contract in hdp_sr.h): bf16 W = sr(float32(W) + dW) from
+// the float32 sum, 8 B per element like merge_chunk_kernel<true> and in its form -- one flat chunk space
+// over the items, a workgroup owns 2 kMergeU x 256 consecutive 8-element vectors at a time, every load of
+// the chunk issued before its first store, non-temporal both ways.  One Philox block per vector (element
+// index e = elem0 + 8 i, a multiple of 8): ~40 32-bit multiplies and ~60 other VALU operations per 64 bytes
+// of traffic.  The n % 8 tail elements of an item are merged one per lane by the item's first chunk (an
+// item shorter than one vector still owns that chunk).  Items that cannot take the vector path (W or dW off
+// 16 bytes, elem0 % 8 != 0) run merge_sr_scalar_kernel: the same function per element, the same e.
+// ---------------------------------------------------------------------------------------
+struct MergeSrArgs {
+  int n;
+  uint32_t seed_lo, seed_hi;
+  void* W[kMergeGroupMax];
+  const float* dW[kMergeGroupMax];
+  int64_t cnt[kMergeGroupMax];      // elements (vectors: cnt / 8, tail: cnt % 8)
+  uint64_t elem0[kMergeGroupMax];   // element index of the item's first element (% 8 == 0)
+  uint64_t offset[kMergeGroupMax];  // the item's Philox offset
+};
+static_assert(sizeof(MergeSrArgs) <= 4096, "merge sr kernel arguments must stay within 4 KB");
+constexpr int64_t kMergeSrChunk = (int64_t)kEwThreads * 2 * kMergeU;  // vectors per chunk
+
+// chunks an item of cnt > 0 elements owns (at least one: the tail rides on the first)
+__host__ __device__ inline int64_t merge_sr_chunks(int64_t cnt) {
+  const int64_t nv = cnt >> 3;
+  return nv ? (nv + kMergeSrChunk - 1) / kMergeSrChunk : 1;
+}
+
+__global__ __launch_bounds__(kEwThreads) void merge_sr_chunk_kernel(MergeSrArgs ga) {
+  constexpr int U = 2 * kMergeU;
+  constexpr int64_t CH = kMergeSrChunk;
+  int it = 0;
+  int64_t base = 0, nch = merge_sr_chunks(ga.cnt[0]);    // item it owns chunks [base, base + nch)
+  for (int64_t c = blockIdx.x;; c += gridDim.x) {        // c, it, base: workgroup-uniform
+    while (c >= base + nch) {
+      base += nch;
+      if (++it == ga.n) return;
+      nch = merge_sr_chunks(ga.cnt[it]);
+    }
+    const int64_t cnt = ga.cnt[it], nv = cnt >> 3;
+    const int64_t v0 = (c - base) * CH + threadIdx.x;
+    const uint64_t off = ga.offset[it], e0 = ga.elem0[it];
+    const SrKey key{ga.seed_lo, ga.seed_hi, static_cast<uint32_t>(off), static_cast<uint32_t>(off >> 32)};
+    const HDP_GLOBAL f32x4* D4 = reinterpret_cast<const HDP_GLOBAL f32x4*>(gptr(ga.dW[it]));
+    HDP_GLOBAL u16x8* W8 = reinterpret_cast<HDP_GLOBAL u16x8*>(gptr(reinterpret_cast<uint16_t*>(ga.W[it])));
+    u16x8 w[U];
+    f32x4 d0[U], d1[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = v0 + u * kEwThreads;
+      if (i < nv) {
+        d0[u] = __builtin_nontemporal_load(D4 + 2 * i);
+        d1[u] = __builtin_nontemporal_load(D4 + 2 * i + 1);
+        w[u] = __builtin_nontemporal_load(W8 + i);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = v0 + u * kEwThreads;
+      if (i < nv) {
+        const Philox4 rb = sr_block((e0 >> 3) + static_cast<uint64_t>(i), key);  // (elem0 % 8 == 0)
+        const u32x4 wv = __builtin_bit_cast(u32x4, w[u]);
+        u32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {  // word k: elements 2k (low halves) and 2k + 1 (high halves)
+          const f32x4& dd = k < 2 ? d0[u] : d1[u];
+          const float s0 = __uint_as_float(wv[k] << 16) + dd[(2 * k) & 3];
+          const float s1 = __uint_as_float(wv[k] & 0xffff0000u) + dd[(2 * k + 1) & 3];
+          o[k] = sr_round(__float_as_uint(s0), rb.w[k] & 0xFFFFu) | (sr_round(__float_as_uint(s1), rb.w[k] >> 16) << 16);
+        }
+        __builtin_nontemporal_store(__builtin_bit_cast(u16x8, o), W8 + i);
+      }
+    }
+    if (c == base) {  // the item's first chunk: the cnt % 8 tail elements, one per lane
+      const int64_t j = 8 * nv + threadIdx.x;
+      if (threadIdx.x < 8 && j < cnt) {
+        HDP_GLOBAL uint16_t* W1 = gptr(reinterpret_cast<uint16_t*>(ga.W[it]));
+        const float d = *gptr(ga.dW[it] + j);
+        W1[j] = sr_merge1(W1[j], d, sr_r16(e0 + static_cast<uint64_t>(j), key));
+      }
+    }
+  }
+}
+
+// element-wise form (an item off the vector path's alignment): element j has e = elem0 + j
+__global__ void merge_sr_scalar_kernel(uint16_t* W, const float* dW, int64_t n, uint64_t elem0, SrKey key) {
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x)
+    W[j] = sr_merge1(W[j], dW[j], sr_r16(elem0 + static_cast<uint64_t>(j), key));
+}
+
+// ---------------------------------------------------------------------------------------
 // Adam on factors.  Every operation is rounded separately (contract(off) on plain operators:
 // HIP's __fmul_rn / __fadd_rn are header-scope * and + that hipcc still fuses into FMAs) so the
 // float32 result follows torch's op-by-op evaluation of hp:356-373 (AdamScalars, adam1 and
@@ -568,6 +659,64 @@ extern "C" int hdp_merge_group(int n, const hdp_merge_item* items, int w_dtype, 
     ga.dW[ga.n] = it.dW;
     ga.nv[ga.n] = it.n / vec;
     bytes += (w_dtype == HDP_F32 ? 12.0 : 8.0) * it.n;
+    if (++ga.n == kMergeGroupMax) {
+      const int rc = launch();
+      if (rc) return rc;
+    }
+  }
+  return launch();
+}
+
+extern "C" int hdp_merge_group_sr(int n, const hdp_merge_sr_item* items, uint64_t seed, void* stream) {
+  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "hdp_merge_group_sr: bad item list");
+  for (int i = 0; i < n; ++i) {  // all of it before the first launch
+    const hdp_merge_sr_item& it = items[i];
+    HDP_CHECK_ARG(it.n >= 0 && it.elem0 >= 0, "hdp_merge_group_sr: item %d has n < 0 or elem0 < 0", i);
+    HDP_CHECK_ARG(it.n == 0 || (it.W && it.dW), "hdp_merge_group_sr: item %d has a null pointer", i);
+    HDP_CHECK_ARG(it.n == 0 || ((reinterpret_cast<uintptr_t>(it.W) & 1u) == 0 && (reinterpret_cast<uintptr_t>(it.dW) & 3u) == 0),
+                  "hdp_merge_group_sr: item %d: W must be 2-byte and dW 4-byte aligned", i);
+  }
+  hipStream_t st = as_stream(stream);
+  MergeSrArgs ga;
+  ga.n = 0;
+  ga.seed_lo = static_cast<uint32_t>(seed);
+  ga.seed_hi = static_cast<uint32_t>(seed >> 32);
+  double bytes = 0;
+  int64_t chunks = 0;
+  auto launch = [&]() -> int {
+    if (ga.n == 0) return HDP_OK;
+    const unsigned grid = (unsigned)(chunks < kMergeGrid ? chunks : kMergeGrid);
+    {
+      KTimer kt(K_MERGE_SR, st, bytes);
+      hipLaunchKernelGGL(merge_sr_chunk_kernel, dim3(grid), dim3(kEwThreads), 0, st, ga);
+    }
+    HDP_CHECK_LAUNCH();
+    ga.n = 0;
+    bytes = 0;
+    chunks = 0;
+    return HDP_OK;
+  };
+  for (int i = 0; i < n; ++i) {
+    const hdp_merge_sr_item& it = items[i];
+    if (it.n == 0) continue;
+    if (!aligned16(it.W) || !aligned16(it.dW) || it.elem0 % 8 != 0) {  // this item element-wise
+      int blocks = (int)((it.n + 255) / 256);
+      if (blocks > 2048) blocks = 2048;
+      {
+        KTimer kt(K_MERGE_SR, st, 8.0 * it.n);
+        hipLaunchKernelGGL(merge_sr_scalar_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<uint16_t*>(it.W),
+                           it.dW, it.n, static_cast<uint64_t>(it.elem0), sr_key(seed, it.offset));
+      }
+      HDP_CHECK_LAUNCH();
+      continue;
+    }
+    ga.W[ga.n] = it.W;
+    ga.dW[ga.n] = it.dW;
+    ga.cnt[ga.n] = it.n;
+    ga.elem0[ga.n] = static_cast<uint64_t>(it.elem0);
+    ga.offset[ga.n] = it.offset;
+    chunks += merge_sr_chunks(it.n);
+    bytes += 8.0 * it.n;
     if (++ga.n == kMergeGroupMax) {
       const int rc = launch();
       if (rc) return rc;

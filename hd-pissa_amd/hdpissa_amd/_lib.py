@@ -41,6 +41,12 @@ class MergeItem(ctypes.Structure):
     _fields_ = [("W", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("n", ctypes.c_int64)]
 
 
+class MergeSrItem(ctypes.Structure):
+    """hdp_merge_sr_item (include/hdpissa.h)."""
+    _fields_ = [("W", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("n", ctypes.c_int64), ("elem0", ctypes.c_int64),
+                ("offset", ctypes.c_uint64)]
+
+
 class CopyItem(ctypes.Structure):
     """hdp_copy_item (include/hdpissa.h)."""
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
@@ -88,6 +94,7 @@ SIGNATURES = {
     "hdp_merge": (_c_int, [_c_vp, _c_int, _c_vp, _c_i64, _c_vp]),
     "hdp_merge_group": (_c_int, [_c_int, ctypes.POINTER(MergeItem), _c_int, _c_vp]),
     "hdp_merge_group_bf16dw": (_c_int, [_c_int, ctypes.POINTER(MergeItem), _c_vp]),
+    "hdp_merge_group_sr": (_c_int, [_c_int, ctypes.POINTER(MergeSrItem), ctypes.c_uint64, _c_vp]),
     "hdp_fold_bf16": (_c_int, [_c_vp, _c_int, _c_i64, _c_vp, _c_i64, _c_vp]),
     "hdp_copy_group": (_c_int, [_c_int, ctypes.POINTER(CopyItem), _c_vp]),
     "hdp_adam_factors": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,

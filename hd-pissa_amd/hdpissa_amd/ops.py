@@ -379,6 +379,28 @@ class HipOps:
             else:
                 check(lib().hdp_merge_group(len(run), arr, _dt(run[0][0]), _stream()), "hdp_merge_group")
 
+    def merge_group_sr(self, triples, seed: int) -> None:
+        """Stochastic-rounding merge over many ``(W, dW, elem0, offset)`` items (one exchange bucket):
+        bfloat16 W = sr(float32(W) + dW) with dW float32, element j of an item at index ``elem0 + j`` of its
+        module's W, ``offset`` the module's Philox offset of this step (hdp_merge_group_sr; the contract and
+        its numpy replica: hdpissa_amd.rounding)."""
+        from ._lib import MergeSrItem
+        if not triples:
+            return
+        arr = (MergeSrItem * len(triples))()
+        for i, (W, dW, elem0, offset) in enumerate(triples):
+            _need_gpu(W, dW)
+            _f32(dW)
+            if W.dtype != torch.bfloat16:
+                raise TypeError(f"merge_group_sr: W must be bfloat16, got {W.dtype}")
+            if W.numel() != dW.numel() or not W.is_contiguous() or not dW.is_contiguous():
+                raise ValueError("merge_group_sr: W and dW must be contiguous with equal sizes")
+            if int(elem0) < 0:
+                raise ValueError("merge_group_sr: elem0 must be >= 0")
+            arr[i].W, arr[i].dW, arr[i].n = W.data_ptr(), dW.data_ptr(), W.numel()
+            arr[i].elem0, arr[i].offset = int(elem0), int(offset) & _U64
+        check(lib().hdp_merge_group_sr(len(triples), arr, int(seed) & _U64, _stream()), "hdp_merge_group_sr")
+
     def copy_group(self, pairs) -> None:
         """dst <- src for many contiguous (dst, src) pairs of equal byte size (any dtypes) in one launch
         per ``_lib.COPY_GROUP_MAX`` pairs: the shard exchange's pack and scatter (hdp_copy_group)."""

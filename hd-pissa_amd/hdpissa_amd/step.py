@@ -39,6 +39,17 @@ fused Adam-pack read that record in stream order, as they read the probe's error
 0 to W_res.  No host synchronisation.  ``t`` still advances on a skipped step: the bias corrections of the
 following steps run one step ahead of the moments.
 
+Opt-in, off by default (``merge_rounding="stochastic"``, ``sr_seed=``; the reference rounds to nearest): a
+bf16 W takes its update as sr(float32(W) + dW) -- 16 random bits per element added below the bf16 cut of the
+float32 sum (hdpissa_amd.rounding has the contract and its numpy replica) -- because at fine-tuning learning
+rates dW is far below half a bf16 ulp of W and round-to-nearest returns the old weight.  bf16 modules then
+skip the fused Adam-pack and K4's MERGE epilogue: after K3, K4 runs as a STORE plan (float32 dW, the plain
+float32 sum over the ranks' segments -- no per-rank bf16 rounding) into two bucketed float32 buffers, and one
+hdp_merge_group_sr per bucket merges on the same stream; under "allreduce" the bf16 buckets take the plain
+float32 all-reduce instead of the rank-ordered fold.  The random bits depend on (sr_seed, module, t, element)
+only, so every rank -- and under "shard" whichever rank merges a row -- writes the same W.  float32 modules
+take exactly the launches they always took.
+
 Semantics kept from the reference: Adam without weight decay, bias correction with the
 post-increment t (hp:350), A and B never updated (hp:375-376; the deltas are recomputed
 against the *initial* factors every step), grads scaled x1e16 (hp:356-357), bf16 models
@@ -106,8 +117,22 @@ class _ShardBucket:
 
 
 class _ArenaPlan:
-    def __init__(self, arena: FactorArena, exchange: str, bucket_bytes: int):
+    def __init__(self, arena: FactorArena, exchange: str, bucket_bytes: int, sr: bool = False,
+                 sr_bytes: int = 1 << 30):
         self.arena = arena
+        # merge_rounding="stochastic": the bf16 modules' float32 dW goes through HBM -- gather / shard: two
+        # buffers of at most ``sr_bytes`` of dense float32 dW (the all-reduce leg's layout; a module above
+        # the bound has a bucket of its own); allreduce: its own dw_bufs, summed by the plain all-reduce
+        self.sr = sr and any(L.W_res.dtype == torch.bfloat16 for L in arena.layers)
+        self.sr_cap = max(1, sr_bytes // 4)
+        self.sr_bufs: List[torch.Tensor] = []
+        self.sr_turn = 0
+        self.sr_progs: Dict[object, tuple] = {}   # launch programs of _sr_merge, per launch site
+        if self.sr and exchange != "allreduce":
+            sizes = [-(-L.out_features * L.in_features // 4) * 4 for L in arena.layers
+                     if L.W_res.dtype == torch.bfloat16]  # (slots stay 16-byte aligned)
+            n_sr = min(sum(sizes), max(self.sr_cap, max(sizes)))
+            self.sr_bufs = [torch.empty(n_sr, dtype=torch.float32, device=arena.fac.device) for _ in range(2)]
         Wn, F = arena.world_size, arena.F
         dev = arena.fac.device
         n = len(arena.layers)
@@ -154,7 +179,7 @@ class _ArenaPlan:
             cap = max(sum(sizes[a:b]) for a, b in self.a_buckets)
             for a, b in self.a_buckets:
                 n = sum(sizes[a:b])
-                self.a_ordered.append(Wn > 1 and all(arena.layers[i].W_res.dtype == torch.bfloat16 for i in range(a, b)))
+                self.a_ordered.append(Wn > 1 and not self.sr and all(arena.layers[i].W_res.dtype == torch.bfloat16 for i in range(a, b)))
                 self.a_shard.append(-(-n // (8 * Wn)) * 8)
             if any(self.a_ordered):
                 sh = max(s for s, o in zip(self.a_shard, self.a_ordered) if o)
@@ -199,15 +224,28 @@ class HDPissaStep:
 
     def __init__(self, model: nn.Module, world_size: int, rank: int = 0, comm=None, ops=None,
                  exchange: str = "gather", bucket_bytes: Optional[int] = None, beta1: float = 0.9,
-                 beta2: float = 0.999, eps: float = 1e-8, max_grad_norm: Optional[float] = None):
+                 beta2: float = 0.999, eps: float = 1e-8, max_grad_norm: Optional[float] = None,
+                 merge_rounding: str = "nearest", sr_seed: Optional[int] = None):
         if exchange not in ("gather", "allreduce", "shard"):
             raise ValueError("exchange must be 'gather', 'allreduce' or 'shard'")
+        if merge_rounding not in ("nearest", "stochastic"):
+            raise ValueError("merge_rounding must be 'nearest' or 'stochastic'")
         self.layers = [m for _, m in custom_layers(model)]
         if not self.layers:
             raise ValueError("model has no CustomLinearLayer")
         self.world_size, self.rank = world_size, rank
         self.exchange = exchange
         self.beta1, self.beta2, self.eps = beta1, beta2, eps
+        # stochastic-rounding merge of the bf16 modules (off by default: nothing below is built or launched
+        # then).  The rounding stream is a function of (sr_seed, module index, t, element): the same on every
+        # rank, and continued by a resume with the same sr_seed
+        self.merge_rounding = merge_rounding
+        self.sr_seed: Optional[int] = None
+        if merge_rounding == "stochastic":
+            from .rounding import default_sr_seed
+            self.sr_seed = default_sr_seed(torch.initial_seed()) if sr_seed is None else int(sr_seed) & (2 ** 64 - 1)
+            self._layer_index = {id(L): i for i, L in enumerate(self.layers)}
+        sr_bytes = (1 << 30) if bucket_bytes is None else min(1 << 30, bucket_bytes)
         if bucket_bytes is None:
             # gather: ~256 MB of per-rank deltas per all-gather bucket; allreduce: 1 GB of dense
             # float32 dW per bucket (two buffers): bigger K4-store / K5 launches, fewer collectives;
@@ -220,12 +258,16 @@ class HDPissaStep:
             if L._arena.world_size != world_size:
                 raise ValueError("layer world_size differs from the step's world_size")
             arenas.setdefault(id(L._arena), L._arena)
-        self.plans = [_ArenaPlan(a, exchange, bucket_bytes) for a in arenas.values()]
         self.device = self.layers[0].W_res.device
         if ops is None:
             from .ops import default_ops
             ops = default_ops()
         self.ops = ops
+        if merge_rounding == "stochastic" and not hasattr(ops, "merge_group_sr"):
+            raise NotImplementedError(f"the op set {getattr(ops, 'name', ops)!r} has no merge_group_sr: "
+                                      "merge_rounding='stochastic' needs the stochastic-rounding merge kernel")
+        self.plans = [_ArenaPlan(a, exchange, bucket_bytes, merge_rounding == "stochastic", sr_bytes)
+                      for a in arenas.values()]
         if comm is None:  # the arena's init communicator (module-sharded SVD) if it has one
             comm = next((p.arena.comm for p in self.plans if getattr(p.arena, "comm", None) is not None), None)
         if comm is None:
@@ -339,7 +381,10 @@ class HDPissaStep:
             kw["clip"] = clip  # (the gradients of every arena were collected for the norm)
         else:
             self._collect_grads(arena)
-        fused = self._fused_plans(plan, lr, t)
+        self._t = t
+        plan.sr_turn = 0
+        # (stochastic rounding merges from the float32 dW: no MERGE epilogue, so no fused Adam-pack either)
+        fused = None if plan.sr else self._fused_plans(plan, lr, t)
         if fused is not None:
             # K3 folded into K4's operand preparation -- per plan one Adam pass that also
             # writes the delta halves of the H2 panels, then the merge (no standalone Adam / pack)
@@ -380,10 +425,85 @@ class HDPissaStep:
                         arena.fac[oa:], arena.fac[ob:], 0, L.W_res))
         return out
 
+    # -- merge_rounding = "stochastic" ---------------------------------------------------
+    def _sr_offset(self, L) -> int:
+        from .rounding import sr_offset
+        return sr_offset(self._layer_index[id(L)], self._t)
+
+    def _sr_slots(self, src: torch.Tensor, slots) -> list:
+        """The all-reduce leg's merge of one bucket under stochastic rounding: the bf16 modules of ``slots``
+        ((layer, offset into src, n)) merged by one merge_group_sr on the current stream; returns the other
+        (float32) slots for the caller's K5."""
+        sr = [(L.W_res, src[o:o + n], 0, self._sr_offset(L)) for L, o, n in slots if L.W_res.dtype == torch.bfloat16]
+        if sr:
+            self.ops.merge_group_sr(sr, self.sr_seed)
+        return [s for s in slots if s[0].W_res.dtype != torch.bfloat16]
+
+    def _sr_merge(self, plan: _ArenaPlan, key, make_items, dsts, idxs, elem0s=None) -> None:
+        """One launch site of the gather / shard exchanges under stochastic rounding.  ``make_items``: the K4
+        items that would MERGE into ``dsts`` (whole W_res, or the rank's row blocks), ``idxs`` their modules
+        (arena indices), ``elem0s`` the element index of each dst's first element in its W (default 0).
+        Runs of float32 destinations take the MERGE plans they always took.  Runs of bf16 destinations: the
+        same items as STORE plans (no per-rank bf16 rounding: dW is the float32 sum over the segments) into
+        dense float32 buckets of the two sr buffers, each followed by its merge_group_sr on this stream.
+        The launch program is cached while no destination moved."""
+        ops, arena = self.ops, plan.arena
+        ptrs = tuple(d.data_ptr() for d in dsts)
+        cache = plan.sr_progs.get(key)
+        if cache is None or cache[0] != ptrs:
+            items = make_items()
+            if elem0s is None:
+                elem0s = [0] * len(items)
+            prog, k = [], 0
+            while k < len(items):  # one run per destination dtype, in order
+                e = k
+                while e < len(items) and dsts[e].dtype == dsts[k].dtype:
+                    e += 1
+                if dsts[k].dtype != torch.bfloat16:
+                    prog.append(("merge", (key, "f", k), items[k:e], dsts[k:e], None))
+                else:
+                    sizes = [-(-it[0] * it[1] // 4) * 4 for it in items[k:e]]  # slots stay 16-byte aligned
+                    for a, b in _buckets(sizes, plan.sr_cap):
+                        stores, merges, off = [], [], 0
+                        for j in range(k + a, k + b):
+                            n = items[j][0] * items[j][1]
+                            stores.append((items[j][:-1], off, n))
+                            merges.append((dsts[j], off, n, elem0s[j], arena.layers[idxs[j]]))
+                            off += sizes[j - k]
+                        prog.append(("sr", (key, "sr", k + a), stores, None, merges))
+                k = e
+            cache = (ptrs, prog)
+            plan.sr_progs[key] = cache
+        for kind, pkey, its, ds, merges in cache[1]:
+            if kind == "merge":
+                if self.grouped:
+                    for p, _ in plan.delta_plans(pkey, ops, lambda its=its: its, HDP_DW_MERGE, ds):
+                        p.run()
+                else:
+                    for it in its:
+                        ops.delta_gemm(*it, HDP_DW_MERGE, False)
+                continue
+            buf = plan.sr_bufs[plan.sr_turn % 2]
+            plan.sr_turn += 1
+            stores = [it + (buf[off:off + n],) for it, off, n in its]
+            if self.grouped:
+                for p, _ in plan.delta_plans(pkey + (plan.sr_turn % 2,), ops, lambda stores=stores: stores, HDP_DW_STORE,
+                                             [s[-1] for s in stores]):
+                    p.run()
+            else:
+                for s in stores:
+                    ops.delta_gemm(*s, HDP_DW_STORE, False)
+            ops.merge_group_sr([(W, buf[off:off + n], e0, self._sr_offset(L)) for W, off, n, e0, L in merges],
+                               self.sr_seed)
+
     # -- exchange = "gather" -------------------------------------------------------------
     def _gather(self, plan: _ArenaPlan) -> None:
         arena, ops, Wn, F = plan.arena, self.ops, self.world_size, plan.arena.F
         if Wn == 1:
+            if plan.sr:
+                self._sr_merge(plan, "g1", lambda: self._items_w1(arena), [L.W_res for L in arena.layers],
+                               list(range(len(arena.layers))))
+                return
             if self.grouped:
                 for p, _ in plan.delta_plans("g1", ops, lambda: self._items_w1(arena), HDP_DW_MERGE,
                                              [L.W_res for L in arena.layers]):
@@ -408,6 +528,9 @@ class HDPissaStep:
                     out.append((L.out_features, L.in_features, L.r, Wn, base[oa - s:], base[ob - s:], seg,
                                 arena.fac_all.view(-1)[oa:], arena.fac_all.view(-1)[ob:], F, L.W_res))
                 return out
+            if plan.sr:
+                self._sr_merge(plan, ("g", bi), items, [arena.layers[i].W_res for i in range(a, b)], list(range(a, b)))
+                continue
             if self.grouped and self.grouped_multiseg:
                 for p, _ in plan.delta_plans(("g", bi), ops, items, HDP_DW_MERGE,
                                              [arena.layers[i].W_res for i in range(a, b)]):
@@ -505,7 +628,18 @@ class HDPissaStep:
             if self.on_gpu:
                 cur.wait_event(events[gi])  # the delta buckets that cover modules [a, b) (in stream order)
             dsts, pack, scat = self._shard_views(plan, sb)
-            if dsts and self.grouped:  # (no rows in the whole bucket: no plan)
+            if dsts and plan.sr:
+                # the own row blocks: element index r0 * in (a multiple of 8: blocks start on multiples of 8
+                # rows), the module's offset -- the bits any rank would give these rows
+                idxs, elem0s = [], []
+                for i in range(sb.a, sb.b):
+                    L = plan.arena.layers[i]
+                    r0, r1 = shard_rows(L.out_features, Wn, self.rank)
+                    if r1 > r0:
+                        idxs.append(i)
+                        elem0s.append(r0 * L.in_features)
+                self._sr_merge(plan, ("s", bi), lambda sb=sb: self._shard_items(plan, sb, self.rank), dsts, idxs, elem0s)
+            elif dsts and self.grouped:  # (no rows in the whole bucket: no plan)
                 for p, _ in plan.delta_plans(("s", bi), ops, lambda sb=sb: self._shard_items(plan, sb, self.rank),
                                              HDP_DW_MERGE, dsts):
                     p.run()
@@ -563,7 +697,10 @@ class HDPissaStep:
             if self.on_gpu and self.world_size == 1:
                 # the all-reduce of one rank is the identity: the bucket's K5 follows its K4 on the
                 # same stream (a side-stream merge would only contend with the next K4 for HBM)
-                ops.merge_group([(L.W_res, buf[o:o + n].view_as(L.W_res)) for L, o, n in slots])
+                if plan.sr:
+                    slots = self._sr_slots(buf, slots)
+                if slots:
+                    ops.merge_group([(L.W_res, buf[o:o + n].view_as(L.W_res)) for L, o, n in slots])
             elif self.on_gpu:
                 computed = torch.cuda.Event()
                 computed.record(cur)
@@ -603,6 +740,10 @@ class HDPissaStep:
         else:
             self.comm.allreduce_sum(buf[:off])
             src = buf
+            if plan.sr:  # bf16 W: the plain float32 sum over ranks, rounded once (no rank-ordered fold)
+                slots = self._sr_slots(src, slots)
+                if not slots:
+                    return
         if hasattr(ops, "merge_group"):  # the bucket's K5 as one launch
             ops.merge_group([(L.W_res, src[o:o + n].view_as(L.W_res)) for L, o, n in slots])
         else:
@@ -615,16 +756,23 @@ _STEPPERS: Dict[int, HDPissaStep] = {}
 
 def hd_pissa_step(model: nn.Module, lr: float, t: int, world_size: int, rank: int = 0, beta1: float = 0.9,
                   beta2: float = 0.999, epsilon: float = 1e-8, exchange: str = "gather", comm=None,
-                  ops=None, max_grad_norm: Optional[float] = None) -> HDPissaStep:
+                  ops=None, max_grad_norm: Optional[float] = None, merge_rounding: str = "nearest",
+                  sr_seed: Optional[int] = None) -> HDPissaStep:
     """Functional form of the reference block hp:352-398 (one call per optimizer step).
     The step object (plan, buffers, streams) is cached per model.  ``max_grad_norm``: clip the global
     gradient norm and skip non-finite steps on the device (HDPissaStep; None, the default: the reference's
-    step)."""
+    step).  ``merge_rounding="stochastic"`` (with ``sr_seed``): bf16 weights take the update by stochastic
+    rounding from the float32 sum (HDPissaStep; "nearest", the default: the reference's merge)."""
     st = _STEPPERS.get(id(model))
     mgn = None if max_grad_norm is None else float(max_grad_norm)
-    if st is None or st.exchange != exchange or st.max_grad_norm != mgn:
+    seed = None
+    if merge_rounding == "stochastic":
+        from .rounding import default_sr_seed
+        seed = default_sr_seed(torch.initial_seed()) if sr_seed is None else int(sr_seed) & (2 ** 64 - 1)
+    if st is None or st.exchange != exchange or st.max_grad_norm != mgn or st.merge_rounding != merge_rounding \
+            or st.sr_seed != seed:
         st = HDPissaStep(model, world_size, rank, comm=comm, ops=ops, exchange=exchange, beta1=beta1, beta2=beta2,
-                         eps=epsilon, max_grad_norm=max_grad_norm)
+                         eps=epsilon, max_grad_norm=max_grad_norm, merge_rounding=merge_rounding, sr_seed=sr_seed)
         _STEPPERS[id(model)] = st
     st.step(lr, t)
     return st

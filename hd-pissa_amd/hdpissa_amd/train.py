@@ -18,6 +18,10 @@ and skips a non-finite step on the device (HDPissaStep).  ``grad_norm_list`` the
 optimizer step and ``skipped_steps`` the running count of skipped ones.  With ``loss_sync="step"`` the
 loss read-back moves behind the step and fetches the step's clip record in the same transfer: still one
 synchronisation per optimizer step.
+
+Added (opt-in, ``merge_rounding="stochastic"``, ``sr_seed=``; the reference rounds to nearest): bf16 weights
+take the step's update by stochastic rounding from the float32 sum (HDPissaStep).  Nothing is added to the
+checkpoint: the rounding stream is a function of ``t`` and ``sr_seed``.
 """
 from __future__ import annotations
 
@@ -36,7 +40,8 @@ class HDPissaTrainer:
                  accumulation_steps: int = 1, warmup_steps: int = 0, warmup_ratio: float = 0.0,
                  schedule: str = "cosine", exchange: str = "gather", loss_sync: str = "step", comm=None, ops=None,
                  beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, merge_rounding: str = "nearest",
+                 sr_seed: Optional[int] = None):
         if loss_sync not in ("step", "micro"):
             raise ValueError("loss_sync must be 'step' or 'micro'")
         if accumulation_steps < 1:
@@ -53,7 +58,8 @@ class HDPissaTrainer:
         self.accumulation_steps = accumulation_steps
         self.loss_sync = loss_sync
         self.stepper = HDPissaStep(model, world_size, rank, comm=comm, ops=ops, exchange=exchange, beta1=beta1,
-                                   beta2=beta2, eps=eps, max_grad_norm=max_grad_norm)
+                                   beta2=beta2, eps=eps, max_grad_norm=max_grad_norm, merge_rounding=merge_rounding,
+                                   sr_seed=sr_seed)
         self.max_grad_norm = self.stepper.max_grad_norm
         self.grad_norm_list: List[float] = []   # per optimizer step (max_grad_norm set)
         self.skipped_steps = 0                  # optimizer steps skipped for a non-finite gradient norm

@@ -78,6 +78,34 @@ int hdp_merge_group(int n, const hdp_merge_item* items, int w_dtype, void* strea
  * n bf16 values (reinterpreted). */
 int hdp_merge_group_bf16dw(int n, const hdp_merge_item* items, void* stream);
 
+/* Stochastic-rounding merge (merge_rounding="stochastic"; opt-in, the reference has no counterpart): a
+ * bfloat16 W takes a float32 dW as W = sr(float32(W) + dW), rounded from the float32 sum with 16 random
+ * bits per element, so an update far below half a bf16 ulp of its weight survives in expectation where
+ * round-to-nearest returns the old weight.  For element j of an item, e = elem0 + j (the row-major index
+ * o * in + i of the element in its module's W, 64-bit):
+ *   s      = float32(W[j]) + dW[j]                  one IEEE float32 add
+ *   u      = bits(s)
+ *   W[j]   = (u & 0x7F800000) == 0x7F800000 ? round-to-nearest-even bf16 of s (inf stays inf, NaN stays NaN)
+ *                                           : (u + r16(e)) >> 16
+ *   words  = philox4x32_10(counter = (lo32(e >> 3), hi32(e >> 3), lo32(offset), hi32(offset)),
+ *                          key = (lo32(seed), hi32(seed)))
+ *   r16(e) = (words[(e & 7) >> 1] >> (16 * (e & 1))) & 0xFFFF
+ * A finite s that is a bf16 value keeps its bits; a carry into the exponent is correct rounding, to
+ * infinity at the top of the range.  The bits depend on (seed, offset, e, dW) only, not on the launch.
+ * W is bfloat16 only.  Any n >= 0 and any alignment (W 2-byte, dW 4-byte): items with W and dW 16-byte
+ * aligned and elem0 % 8 == 0 move as 16-byte vectors (one Philox block per vector) with an element-wise
+ * tail, any other item element by element; nothing outside [W, W + n) is written.  More than 64 vector
+ * items are split over launches.  items is a HOST array read during the call; a bad item is HDP_EINVAL
+ * before anything is launched.  csrc/hdp_sr.h holds the function, hdpissa_amd/rounding.py its numpy replica. */
+typedef struct {
+  void* W;          /* n bf16 elements */
+  const float* dW;  /* n float32 */
+  int64_t n;
+  int64_t elem0;    /* element index of W[0] in its module's W (>= 0) */
+  uint64_t offset;  /* (module index << 32) | (step counter mod 2^32) */
+} hdp_merge_sr_item;
+int hdp_merge_group_sr(int n, const hdp_merge_sr_item* items, uint64_t seed, void* stream);
+
 /* Rank-ordered bf16 fold -- the rounding order of hp:389-392 for a bfloat16 model:
  *   delta_W_res = zeros_like(W_res) (bf16);  for i in 0..nparts-1:  delta_W_res -= bracket_i
  * i.e. out = 0; out = bf16(out + parts[i]) for i = 0, 1, ... with parts[i] = -bracket_i (float32,
