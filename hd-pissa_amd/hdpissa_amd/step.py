@@ -58,6 +58,7 @@ accumulate dW in bf16 rank by rank (zeros_like(W_res), hp:389).
 from __future__ import annotations
 
 import os
+from contextlib import contextmanager
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -113,7 +114,7 @@ class _ShardBucket:
             block = shard_rows(L.out_features, Wn, 0)[1]
             off += -(-block * L.in_features * L.W_res.element_size() // 16) * 16
         self.nbytes = off
-        self.views = None  # (W_res pointers, dsts, pack, scatter), built on first use (_shard_views)
+        self.views = None  # (W_res pointers, dsts, owners, pack, scatter), built on first use (_shard_views)
 
 
 class _ArenaPlan:
@@ -128,67 +129,99 @@ class _ArenaPlan:
         self.sr_bufs: List[torch.Tensor] = []
         self.sr_turn = 0
         self.sr_progs: Dict[object, tuple] = {}   # launch programs of _sr_merge, per launch site
+        Wn = arena.world_size
         if self.sr and exchange != "allreduce":
-            sizes = [-(-L.out_features * L.in_features // 4) * 4 for L in arena.layers
-                     if L.W_res.dtype == torch.bfloat16]  # (slots stay 16-byte aligned)
-            n_sr = min(sum(sizes), max(self.sr_cap, max(sizes)))
-            self.sr_bufs = [torch.empty(n_sr, dtype=torch.float32, device=arena.fac.device) for _ in range(2)]
-        Wn, F = arena.world_size, arena.F
-        dev = arena.fac.device
-        n = len(arena.layers)
-        # gather: buckets over the delta arena (module-aligned ranges)
-        ends = [arena.offsets[i + 1][0] if i + 1 < n else F for i in range(n)]
-        starts = [arena.offsets[i][0] for i in range(n)]
-        self.g_buckets = []
+            self._build_sr()
         # (shard: bucket_bytes bounds the W buckets; the delta buckets keep gather's default bound)
-        g_bytes = min(bucket_bytes, 256 << 20) if exchange == "shard" else bucket_bytes
-        for a, b in _buckets([ends[i] - starts[i] for i in range(n)], max(1, g_bytes // 4 // max(Wn, 1))):
-            self.g_buckets.append((a, b, starts[a], ends[b - 1]))
-        self.delta_all = torch.empty(Wn * F, dtype=torch.float32, device=dev) \
-            if (exchange in ("gather", "shard") and Wn > 1) else None
-        # shard: W buckets over dense W bytes, split where the dtype changes; two send and two gather
-        # buffers (bytes) sized for the longest shard
+        self._build_gather(min(bucket_bytes, 256 << 20) if exchange == "shard" else bucket_bytes,
+                           exchange in ("gather", "shard") and Wn > 1)
         self.s_buckets: List[_ShardBucket] = []
         self.s_send: List[torch.Tensor] = []
         self.s_gath: List[torch.Tensor] = []
         if exchange == "shard" and Wn > 1:
-            run = 0
-            for i in range(1, n + 1):
-                if i == n or arena.layers[i].W_res.dtype != arena.layers[run].W_res.dtype:
-                    sizes = [L.W_res.numel() * L.W_res.element_size() for L in arena.layers[run:i]]
-                    self.s_buckets += [_ShardBucket(arena.layers, run + a, run + b, Wn)
-                                       for a, b in _buckets(sizes, max(1, bucket_bytes))]
-                    run = i
-            cap = max(sb.nbytes for sb in self.s_buckets)
-            self.s_send = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
-            self.s_gath = [torch.empty(Wn * cap, dtype=torch.uint8, device=dev) for _ in range(2)]
-        # allreduce: buckets over dense dW sizes
+            self._build_shard(bucket_bytes)
         self.a_buckets = []
         self.dw_bufs: List[torch.Tensor] = []
-        # rank-ordered bf16 exchange (bf16 buckets at Wn > 1): per bucket the 1/Wn shard length (a
-        # multiple of 8 elements), the all-to-all receive buffers, the folded bf16 shards and the
-        # all-gathered bf16 dW (double-buffered like dw_bufs)
         self.a_ordered: List[bool] = []
         self.a_shard: List[int] = []
         self.o_recv: List[torch.Tensor] = []
         self.o_shard: List[torch.Tensor] = []
         self.o_gath: List[torch.Tensor] = []
         if exchange == "allreduce":
-            sizes = [L.out_features * L.in_features for L in arena.layers]
-            self.a_buckets = _buckets(sizes, max(1, bucket_bytes // 4))
-            cap = max(sum(sizes[a:b]) for a, b in self.a_buckets)
-            for a, b in self.a_buckets:
-                n = sum(sizes[a:b])
-                self.a_ordered.append(Wn > 1 and not self.sr and all(arena.layers[i].W_res.dtype == torch.bfloat16 for i in range(a, b)))
-                self.a_shard.append(-(-n // (8 * Wn)) * 8)
-            if any(self.a_ordered):
-                sh = max(s for s, o in zip(self.a_shard, self.a_ordered) if o)
-                cap = max(cap, Wn * sh)
-                self.o_recv = [torch.empty(Wn * sh, dtype=torch.float32, device=dev) for _ in range(2)]
-                self.o_shard = [torch.empty(sh, dtype=torch.bfloat16, device=dev) for _ in range(2)]
-                self.o_gath = [torch.empty(Wn * sh, dtype=torch.bfloat16, device=dev) for _ in range(2)]
-            self.dw_bufs = [torch.zeros(cap, dtype=torch.float32, device=dev) for _ in range(2)]
+            self._build_allreduce(bucket_bytes)
         self.plans: Dict[tuple, list] = {}   # grouped K4 launches, built on first use
+
+    def _build_sr(self) -> None:
+        arena = self.arena
+        sizes = [-(-L.out_features * L.in_features // 4) * 4 for L in arena.layers
+                 if L.W_res.dtype == torch.bfloat16]  # (slots stay 16-byte aligned)
+        n = min(sum(sizes), max(self.sr_cap, max(sizes)))
+        self.sr_bufs = [torch.empty(n, dtype=torch.float32, device=arena.fac.device) for _ in range(2)]
+
+    def _build_gather(self, bucket_bytes: int, gathered: bool) -> None:
+        """Buckets over the delta arena (module-aligned ranges): (a, b, start, end) for modules [a, b);
+        ``g_of[i]``: the bucket of module i; ``delta_all``: every rank's deltas, bucket by bucket."""
+        arena, Wn, F = self.arena, self.arena.world_size, self.arena.F
+        n = len(arena.layers)
+        ends = [arena.offsets[i + 1][0] if i + 1 < n else F for i in range(n)]
+        starts = [arena.offsets[i][0] for i in range(n)]
+        self.g_buckets = [(a, b, starts[a], ends[b - 1]) for a, b in
+                          _buckets([ends[i] - starts[i] for i in range(n)], max(1, bucket_bytes // 4 // max(Wn, 1)))]
+        self.g_of = [gi for gi, (a, b, _, _) in enumerate(self.g_buckets) for _ in range(a, b)]
+        self.delta_all = torch.empty(Wn * F, dtype=torch.float32, device=arena.fac.device) if gathered else None
+
+    def _build_shard(self, bucket_bytes: int) -> None:
+        """W buckets over dense W bytes, split where the dtype changes; two send and two gather buffers
+        (bytes) sized for the longest shard."""
+        layers, Wn, dev = self.arena.layers, self.arena.world_size, self.arena.fac.device
+        run, n = 0, len(layers)
+        for i in range(1, n + 1):
+            if i == n or layers[i].W_res.dtype != layers[run].W_res.dtype:
+                sizes = [L.W_res.numel() * L.W_res.element_size() for L in layers[run:i]]
+                self.s_buckets += [_ShardBucket(layers, run + a, run + b, Wn)
+                                   for a, b in _buckets(sizes, max(1, bucket_bytes))]
+                run = i
+        cap = max(sb.nbytes for sb in self.s_buckets)
+        self.s_send = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.s_gath = [torch.empty(Wn * cap, dtype=torch.uint8, device=dev) for _ in range(2)]
+
+    def _build_allreduce(self, bucket_bytes: int) -> None:
+        """Buckets over dense dW sizes and the two float32 dW buffers.  Rank-ordered bf16 exchange (bf16
+        buckets at Wn > 1): per bucket the 1/Wn shard length (a multiple of 8 elements), the all-to-all
+        receive buffers, the folded bf16 shards and the all-gathered bf16 dW (double-buffered like dw_bufs)."""
+        layers, Wn, dev = self.arena.layers, self.arena.world_size, self.arena.fac.device
+        sizes = [L.out_features * L.in_features for L in layers]
+        self.a_buckets = _buckets(sizes, max(1, bucket_bytes // 4))
+        cap = max(sum(sizes[a:b]) for a, b in self.a_buckets)
+        for a, b in self.a_buckets:
+            self.a_ordered.append(Wn > 1 and not self.sr and all(L.W_res.dtype == torch.bfloat16 for L in layers[a:b]))
+            self.a_shard.append(-(-sum(sizes[a:b]) // (8 * Wn)) * 8)
+        if any(self.a_ordered):
+            sh = max(s for s, o in zip(self.a_shard, self.a_ordered) if o)
+            cap = max(cap, Wn * sh)
+            self.o_recv = [torch.empty(Wn * sh, dtype=torch.float32, device=dev) for _ in range(2)]
+            self.o_shard = [torch.empty(sh, dtype=torch.bfloat16, device=dev) for _ in range(2)]
+            self.o_gath = [torch.empty(Wn * sh, dtype=torch.bfloat16, device=dev) for _ in range(2)]
+        self.dw_bufs = [torch.zeros(cap, dtype=torch.float32, device=dev) for _ in range(2)]
+
+    @staticmethod
+    def local_item(arena: FactorArena, i: int, dst: torch.Tensor):
+        """The K4 item of module i on this rank's own deltas and factors (one segment), writing ``dst``."""
+        L = arena.layers[i]
+        oa, ob = arena.offsets[i]
+        return (L.out_features, L.in_features, L.r, 1, arena.delta[oa:], arena.delta[ob:], 0,
+                arena.fac[oa:], arena.fac[ob:], 0, dst)
+
+    def gathered_item(self, i: int):
+        """The K4 item of module i on every rank's deltas and factors (Wn segments: the deltas relative to
+        the module's delta bucket in ``delta_all``, the factors in ``fac_all``), merging into W_res."""
+        arena, Wn = self.arena, self.arena.world_size
+        _, _, s, e = self.g_buckets[self.g_of[i]]
+        base, fac = self.delta_all[Wn * s:], arena.fac_all.view(-1)
+        L = arena.layers[i]
+        oa, ob = arena.offsets[i]
+        return (L.out_features, L.in_features, L.r, Wn, base[oa - s:], base[ob - s:], e - s,
+                fac[oa:], fac[ob:], arena.F, L.W_res)
 
     def delta_plans(self, key, ops, make_items, mode, dsts) -> list:
         """Grouped K4 plans for one launch site (cached; rebuilt if a destination moved).
@@ -219,6 +252,68 @@ class _ArenaPlan:
         return ops.delta_plan([it for it, _ in run], mode, rnd), [d for _, d in run]
 
 
+class _Pipeline:
+    """The side-stream pipeline of one exchange: work for the side stream is ordered after what the main
+    stream has enqueued, and the main stream waits for an event of the side stream before it reuses a buffer
+    pair (two pairs, ``q`` = bucket % 2) and, at the end, for the last one.  On the CPU (``side`` None:
+    synchronous collectives) the work runs in place and every wait is a no-op."""
+
+    def __init__(self, device, side):
+        self.side = side
+        self.cur = torch.cuda.current_stream(device) if side is not None else None
+        self.freed = [None, None]
+        self.last = None
+
+    def wait(self, ev) -> None:
+        """The main stream waits for ``ev`` (None: nothing to wait for)."""
+        if ev is not None:
+            self.cur.wait_event(ev)
+
+    def acquire(self, q: int) -> None:
+        """Before the main stream writes buffer pair q: the side-stream work that read it is done."""
+        self.wait(self.freed[q])
+
+    def mark(self):
+        """An event at the side stream's current position (None on the CPU)."""
+        if self.side is None:
+            return None
+        ev = torch.cuda.Event()
+        ev.record(self.side)
+        return ev
+
+    @contextmanager
+    def on_side(self, q: Optional[int] = None):
+        """The body runs on the side stream, after everything the main stream has enqueued so far; with
+        ``q`` its end is marked as the release of buffer pair q."""
+        if self.side is None:
+            yield
+            return
+        ready = torch.cuda.Event()
+        ready.record(self.cur)
+        with torch.cuda.stream(self.side):
+            self.side.wait_event(ready)
+            yield
+            if q is not None:
+                self.freed[q] = self.last = self.mark()
+
+    def drain(self) -> None:
+        self.wait(self.last)
+
+
+def _copy_pairs(pairs) -> None:
+    for dst, src in pairs:
+        dst.copy_(src)
+
+
+def _sr_seed(merge_rounding: str, sr_seed: Optional[int]) -> Optional[int]:
+    """The seed a stepper runs with: None under "nearest", else ``sr_seed`` as an unsigned 64-bit value
+    (default: derived from torch's initial seed)."""
+    if merge_rounding != "stochastic":
+        return None
+    from .rounding import default_sr_seed
+    return default_sr_seed(torch.initial_seed()) if sr_seed is None else int(sr_seed) & (2 ** 64 - 1)
+
+
 class HDPissaStep:
     """Stateful step object: holds the exchange plan, bucket buffers, side stream and events."""
 
@@ -240,10 +335,8 @@ class HDPissaStep:
         # then).  The rounding stream is a function of (sr_seed, module index, t, element): the same on every
         # rank, and continued by a resume with the same sr_seed
         self.merge_rounding = merge_rounding
-        self.sr_seed: Optional[int] = None
+        self.sr_seed = _sr_seed(merge_rounding, sr_seed)
         if merge_rounding == "stochastic":
-            from .rounding import default_sr_seed
-            self.sr_seed = default_sr_seed(torch.initial_seed()) if sr_seed is None else int(sr_seed) & (2 ** 64 - 1)
             self._layer_index = {id(L): i for i, L in enumerate(self.layers)}
         sr_bytes = (1 << 30) if bucket_bytes is None else min(1 << 30, bucket_bytes)
         if bucket_bytes is None:
@@ -277,12 +370,14 @@ class HDPissaStep:
         self.on_gpu = self.device.type == "cuda"
         self.side = torch.cuda.Stream(device=self.device) if self.on_gpu else None
         # grouped persistent K4 (one launch per bucket); HDP_DELTA_GROUPED=0 -> one launch per module
-        self.grouped = hasattr(ops, "delta_plan") and os.environ.get("HDP_DELTA_GROUPED", "1") != "0"
-        # K = 2 r Wn > 32 (gathered segments): the grouped plan runs the packed bf16x3 kernel
-        # (tools/delta_bench.py, 56 LLaMA-7B modules: Wn 2 / 4 / 8 = 2.8 / 3.8 / 6.3 ms vs
+        # (K = 2 r Wn > 32, gathered segments: the grouped plan runs the packed bf16x3 kernel --
+        # tools/delta_bench.py, 56 LLaMA-7B modules: Wn 2 / 4 / 8 = 2.8 / 3.8 / 6.3 ms vs
         # 3.7 / 5.3 / 8.5 ms for per-module f32 launches)
-        self.grouped_multiseg = self.grouped
+        self.grouped = hasattr(ops, "delta_plan") and os.environ.get("HDP_DELTA_GROUPED", "1") != "0"
         self._fuse_adam = os.environ.get("HDP_FUSED_ADAM", "1") != "0"
+        # the bucket's K5 and the shard exchange's pack / scatter as one launch where the op set has them
+        self._merge_group = getattr(ops, "merge_group", None) or (lambda pairs: [ops.merge(W, dW) for W, dW in pairs])
+        self._copy = getattr(ops, "copy_group", None) or _copy_pairs
         # global gradient-norm clipping + non-finite-step skip (off by default: nothing below is built or
         # launched then).  c > 0; math.inf = measure and guard only
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -409,186 +504,150 @@ class HDPissaStep:
         from .ops import adam_delta_bound
         if adam_delta_bound(t, lr, self.beta1, self.beta2) is None:
             return None
-        arena = plan.arena
-        plans = plan.delta_plans("g1", self.ops, lambda: self._items_w1(arena), HDP_DW_MERGE,
-                                 [L.W_res for L in arena.layers])
+        plans = self._k4_w1(plan, run=False)
         if all(getattr(p, "fused_adam", None) is not None and p.fused_adam() for p, _ in plans):
             return plans
         return None
 
     @staticmethod
     def _items_w1(arena: FactorArena):
-        out = []
-        for i, L in enumerate(arena.layers):
-            oa, ob = arena.offsets[i]
-            out.append((L.out_features, L.in_features, L.r, 1, arena.delta[oa:], arena.delta[ob:], 0,
-                        arena.fac[oa:], arena.fac[ob:], 0, L.W_res))
-        return out
+        return [_ArenaPlan.local_item(arena, i, L.W_res) for i, L in enumerate(arena.layers)]
+
+    def _k4(self, plan: _ArenaPlan, key, make_items, mode: int, dsts, run: bool = True):
+        """K4 over the items ``make_items()`` returns, item j writing ``dsts[j]`` -- the one place K4 is
+        launched from.  Grouped (the default): the plans cached under ``key``, one per run of one destination
+        dtype, rebuilt if a destination moved; returns them (``run=False``: without launching).
+        HDP_DELTA_GROUPED=0: one launch per module.  bf16 destinations round per rank (hp:389-392)."""
+        if self.grouped:
+            plans = plan.delta_plans(key, self.ops, make_items, mode, dsts)
+            if run:
+                for p, _ in plans:
+                    p.run()
+            return plans
+        for it, d in zip(make_items(), dsts):
+            self.ops.delta_gemm(*it, mode, d.dtype == torch.bfloat16)
+        return None
+
+    def _k4_w1(self, plan: _ArenaPlan, run: bool = True):
+        """World size 1: every module's merge on this rank's own deltas."""
+        arena = plan.arena
+        return self._k4(plan, "g1", lambda: self._items_w1(arena), HDP_DW_MERGE, [L.W_res for L in arena.layers], run)
 
     # -- merge_rounding = "stochastic" ---------------------------------------------------
     def _sr_offset(self, L) -> int:
         from .rounding import sr_offset
         return sr_offset(self._layer_index[id(L)], self._t)
 
+    def _merge_sr(self, entries) -> None:
+        """One merge_group_sr on the current stream over ``(W rows, float32 dW, element index of the first
+        element in its W, layer)`` entries: the layer gives the module's Philox offset of this step."""
+        self.ops.merge_group_sr([(W, dW, e0, self._sr_offset(L)) for W, dW, e0, L in entries], self.sr_seed)
+
     def _sr_slots(self, src: torch.Tensor, slots) -> list:
         """The all-reduce leg's merge of one bucket under stochastic rounding: the bf16 modules of ``slots``
         ((layer, offset into src, n)) merged by one merge_group_sr on the current stream; returns the other
         (float32) slots for the caller's K5."""
-        sr = [(L.W_res, src[o:o + n], 0, self._sr_offset(L)) for L, o, n in slots if L.W_res.dtype == torch.bfloat16]
+        sr = [(L.W_res, src[o:o + n], 0, L) for L, o, n in slots if L.W_res.dtype == torch.bfloat16]
         if sr:
-            self.ops.merge_group_sr(sr, self.sr_seed)
+            self._merge_sr(sr)
         return [s for s in slots if s[0].W_res.dtype != torch.bfloat16]
 
-    def _sr_merge(self, plan: _ArenaPlan, key, make_items, dsts, idxs, elem0s=None) -> None:
+    def _sr_merge(self, plan: _ArenaPlan, key, make_items, dsts, owners) -> None:
         """One launch site of the gather / shard exchanges under stochastic rounding.  ``make_items``: the K4
-        items that would MERGE into ``dsts`` (whole W_res, or the rank's row blocks), ``idxs`` their modules
-        (arena indices), ``elem0s`` the element index of each dst's first element in its W (default 0).
+        items that would MERGE into ``dsts`` (whole W_res, or the rank's row blocks), ``owners`` their layers.
         Runs of float32 destinations take the MERGE plans they always took.  Runs of bf16 destinations: the
         same items as STORE plans (no per-rank bf16 rounding: dW is the float32 sum over the segments) into
         dense float32 buckets of the two sr buffers, each followed by its merge_group_sr on this stream.
-        The launch program is cached while no destination moved."""
-        ops, arena = self.ops, plan.arena
+        The launch program (_sr_program) is cached while no destination moved."""
         ptrs = tuple(d.data_ptr() for d in dsts)
         cache = plan.sr_progs.get(key)
         if cache is None or cache[0] != ptrs:
-            items = make_items()
-            if elem0s is None:
-                elem0s = [0] * len(items)
-            prog, k = [], 0
-            while k < len(items):  # one run per destination dtype, in order
-                e = k
-                while e < len(items) and dsts[e].dtype == dsts[k].dtype:
-                    e += 1
-                if dsts[k].dtype != torch.bfloat16:
-                    prog.append(("merge", (key, "f", k), items[k:e], dsts[k:e], None))
-                else:
-                    sizes = [-(-it[0] * it[1] // 4) * 4 for it in items[k:e]]  # slots stay 16-byte aligned
-                    for a, b in _buckets(sizes, plan.sr_cap):
-                        stores, merges, off = [], [], 0
-                        for j in range(k + a, k + b):
-                            n = items[j][0] * items[j][1]
-                            stores.append((items[j][:-1], off, n))
-                            merges.append((dsts[j], off, n, elem0s[j], arena.layers[idxs[j]]))
-                            off += sizes[j - k]
-                        prog.append(("sr", (key, "sr", k + a), stores, None, merges))
-                k = e
-            cache = (ptrs, prog)
-            plan.sr_progs[key] = cache
-        for kind, pkey, its, ds, merges in cache[1]:
-            if kind == "merge":
-                if self.grouped:
-                    for p, _ in plan.delta_plans(pkey, ops, lambda its=its: its, HDP_DW_MERGE, ds):
-                        p.run()
-                else:
-                    for it in its:
-                        ops.delta_gemm(*it, HDP_DW_MERGE, False)
+            cache = plan.sr_progs[key] = (ptrs, self._sr_program(key, make_items(), dsts, owners, plan.sr_cap))
+        for bf16, pkey, its, ds, slots in cache[1]:
+            if not bf16:
+                self._k4(plan, pkey, lambda: its, HDP_DW_MERGE, ds)
                 continue
             buf = plan.sr_bufs[plan.sr_turn % 2]
-            plan.sr_turn += 1
-            stores = [it + (buf[off:off + n],) for it, off, n in its]
-            if self.grouped:
-                for p, _ in plan.delta_plans(pkey + (plan.sr_turn % 2,), ops, lambda stores=stores: stores, HDP_DW_STORE,
-                                             [s[-1] for s in stores]):
-                    p.run()
+            plan.sr_turn += 1  # (before the key's parity is taken)
+            stores = [buf[off:off + n] for off, n, _, _ in slots]
+            self._k4(plan, pkey + (plan.sr_turn % 2,), lambda: [it + (s,) for it, s in zip(its, stores)], HDP_DW_STORE,
+                     stores)
+            self._merge_sr([(d, s, e0, L) for d, s, (_, _, e0, L) in zip(ds, stores, slots)])
+
+    @staticmethod
+    def _sr_program(key, items, dsts, owners, cap: int) -> list:
+        """The launch program of one _sr_merge site: per run of one destination dtype, in order, float32:
+        ``(False, plan key, items, dsts, None)``, a MERGE; bf16, per bucket of at most ``cap`` floats:
+        ``(True, plan key, items without dst, dsts, slots)`` -- a STORE into the slots ``(offset, n, elem0,
+        layer)`` of an sr buffer, then the merge of every slot into its dst.  elem0: the element index of the
+        dst's first element in its W -- for a row block r0 * in (a multiple of 8: blocks start on multiples of
+        8 rows); with the module's offset, the bits any rank would give these rows."""
+        prog, k = [], 0
+        while k < len(items):
+            e = k
+            while e < len(items) and dsts[e].dtype == dsts[k].dtype:
+                e += 1
+            if dsts[k].dtype != torch.bfloat16:
+                prog.append((False, (key, "f", k), items[k:e], dsts[k:e], None))
             else:
-                for s in stores:
-                    ops.delta_gemm(*s, HDP_DW_STORE, False)
-            ops.merge_group_sr([(W, buf[off:off + n], e0, self._sr_offset(L)) for W, off, n, e0, L in merges],
-                               self.sr_seed)
+                sizes = [-(-it[0] * it[1] // 4) * 4 for it in items[k:e]]  # slots stay 16-byte aligned
+                for a, b in _buckets(sizes, cap):
+                    slots, off = [], 0
+                    for j in range(k + a, k + b):
+                        elem0 = dsts[j].storage_offset() - owners[j].W_res.storage_offset()
+                        slots.append((off, items[j][0] * items[j][1], elem0, owners[j]))
+                        off += sizes[j - k]
+                    prog.append((True, (key, "sr", k + a), [it[:-1] for it in items[k + a:k + b]], dsts[k + a:k + b], slots))
+            k = e
+        return prog
 
     # -- exchange = "gather" -------------------------------------------------------------
     def _gather(self, plan: _ArenaPlan) -> None:
-        arena, ops, Wn, F = plan.arena, self.ops, self.world_size, plan.arena.F
-        if Wn == 1:
+        layers = plan.arena.layers
+        if self.world_size == 1:
             if plan.sr:
-                self._sr_merge(plan, "g1", lambda: self._items_w1(arena), [L.W_res for L in arena.layers],
-                               list(range(len(arena.layers))))
-                return
-            if self.grouped:
-                for p, _ in plan.delta_plans("g1", ops, lambda: self._items_w1(arena), HDP_DW_MERGE,
-                                             [L.W_res for L in arena.layers]):
-                    p.run()
-                return
-            for it in self._items_w1(arena):
-                ops.delta_gemm(*it, HDP_DW_MERGE, it[-1].dtype == torch.bfloat16)
+                self._sr_merge(plan, "g1", lambda: self._items_w1(plan.arena), [L.W_res for L in layers], layers)
+            else:
+                self._k4_w1(plan)
             return
-        cur = torch.cuda.current_stream(self.device) if self.on_gpu else None
-        events = self._gather_deltas(plan, cur)
-        for bi, (a, b, s, e) in enumerate(plan.g_buckets):
-            if self.on_gpu:
-                cur.wait_event(events[bi])
-            seg = e - s
-            base = plan.delta_all[Wn * s:]
-
-            def items(a=a, b=b, s=s, seg=seg, base=base):
-                out = []
-                for i in range(a, b):
-                    L = arena.layers[i]
-                    oa, ob = arena.offsets[i]
-                    out.append((L.out_features, L.in_features, L.r, Wn, base[oa - s:], base[ob - s:], seg,
-                                arena.fac_all.view(-1)[oa:], arena.fac_all.view(-1)[ob:], F, L.W_res))
-                return out
+        pipe = _Pipeline(self.device, self.side)
+        events = self._gather_deltas(plan, pipe)
+        for bi, (a, b, _, _) in enumerate(plan.g_buckets):
+            pipe.wait(events[bi])
+            items = lambda a=a, b=b: [plan.gathered_item(i) for i in range(a, b)]  # noqa: E731
+            dsts = [L.W_res for L in layers[a:b]]
             if plan.sr:
-                self._sr_merge(plan, ("g", bi), items, [arena.layers[i].W_res for i in range(a, b)], list(range(a, b)))
-                continue
-            if self.grouped and self.grouped_multiseg:
-                for p, _ in plan.delta_plans(("g", bi), ops, items, HDP_DW_MERGE,
-                                             [arena.layers[i].W_res for i in range(a, b)]):
-                    p.run()
-                continue
-            for it in items():
-                ops.delta_gemm(*it, HDP_DW_MERGE, it[-1].dtype == torch.bfloat16)
+                self._sr_merge(plan, ("g", bi), items, dsts, layers[a:b])
+            else:
+                self._k4(plan, ("g", bi), items, HDP_DW_MERGE, dsts)
 
-    def _gather_deltas(self, plan: _ArenaPlan, cur) -> list:
+    def _gather_deltas(self, plan: _ArenaPlan, pipe: _Pipeline) -> list:
         """The bucketed all-gather of the deltas into ``delta_all`` (on the side stream on the GPU);
-        returns one event per delta bucket (none on the CPU, where the collectives are synchronous)."""
+        returns one event per delta bucket (None on the CPU, where the collectives are synchronous)."""
         arena, Wn = plan.arena, self.world_size
         events = []
-        if self.on_gpu:
-            ready = torch.cuda.Event()
-            ready.record(cur)
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ready)
-                for (a, b, s, e) in plan.g_buckets:
-                    self.comm.allgather(arena.delta[s:e], plan.delta_all[Wn * s:Wn * e])
-                    ev = torch.cuda.Event()
-                    ev.record(self.side)
-                    events.append(ev)
-        else:
+        with pipe.on_side():
             for (a, b, s, e) in plan.g_buckets:
                 self.comm.allgather(arena.delta[s:e], plan.delta_all[Wn * s:Wn * e])
+                events.append(pipe.mark())
         return events
 
     # -- exchange = "shard" --------------------------------------------------------------
     def _shard_items(self, plan: _ArenaPlan, sb: _ShardBucket, k: int) -> list:
         """Rank k's K4 items of one W bucket: its row block (``shard_item``) of every module that gives
         it rows, on the gathered deltas and factors as the gather exchange lays them out."""
-        arena, Wn, F = plan.arena, self.world_size, plan.arena.F
-        fac = arena.fac_all.view(-1)
-        items = []
-        gi = 0
-        for i in range(sb.a, sb.b):
-            while plan.g_buckets[gi][1] <= i:
-                gi += 1
-            _, _, s, e = plan.g_buckets[gi]  # the delta bucket that holds module i
-            base = plan.delta_all[Wn * s:]
-            L = arena.layers[i]
-            oa, ob = arena.offsets[i]
-            it = shard_item((L.out_features, L.in_features, L.r, Wn, base[oa - s:], base[ob - s:], e - s,
-                             fac[oa:], fac[ob:], F, L.W_res), Wn, k)
-            if it is not None:
-                items.append(it)
-        return items
+        items = (shard_item(plan.gathered_item(i), self.world_size, k) for i in range(sb.a, sb.b))
+        return [it for it in items if it is not None]
 
     def _shard_views(self, plan: _ArenaPlan, sb: _ShardBucket):
-        """(dsts, pack, scatter) of one W bucket, cached while no W_res moved: this rank's row blocks
-        (the K4 destinations), and per buffer pair the (dst, src) byte ranges that move them into the send
-        buffer and every other rank's rows from the gather buffer into W_res."""
+        """(dsts, owners, pack, scatter) of one W bucket, cached while no W_res moved: this rank's row blocks
+        (the K4 destinations) and their layers, and per buffer pair the (dst, src) byte ranges that move them
+        into the send buffer and every other rank's rows from the gather buffer into W_res."""
         layers, Wn = plan.arena.layers[sb.a:sb.b], self.world_size
         ptrs = tuple(L.W_res.data_ptr() for L in layers)
         if sb.views is not None and sb.views[0] == ptrs:
             return sb.views[1:]
-        dsts, pack, scat = [], ([], []), ([], [])
+        dsts, owners, pack, scat = [], [], ([], []), ([], [])
         for L, off in zip(layers, sb.slots):
             row = L.in_features * L.W_res.element_size()
             for j in range(Wn):
@@ -598,124 +657,64 @@ class HDPissaStep:
                 rows = L.W_res[r0:r1].reshape(-1).view(torch.uint8)
                 if j == self.rank:
                     dsts.append(L.W_res[r0:r1])
+                    owners.append(L)
                 for q in range(2):
                     if j == self.rank:
                         pack[q].append((plan.s_send[q][off:off + (r1 - r0) * row], rows))
                     else:
                         o = j * sb.nbytes + off
                         scat[q].append((rows, plan.s_gath[q][o:o + (r1 - r0) * row]))
-        sb.views = (ptrs, dsts, pack, scat)
-        return dsts, pack, scat
-
-    def _copy(self, pairs) -> None:
-        if hasattr(self.ops, "copy_group"):  # the pack / scatter as one launch
-            self.ops.copy_group(pairs)
-        else:
-            for dst, src in pairs:
-                dst.copy_(src)
+        sb.views = (ptrs, dsts, owners, pack, scat)
+        return sb.views[1:]
 
     def _shard(self, plan: _ArenaPlan) -> None:
-        ops, Wn = self.ops, self.world_size
-        cur = torch.cuda.current_stream(self.device) if self.on_gpu else None
-        events = self._gather_deltas(plan, cur)
-        freed = [None, None]
-        last = None
-        gi = 0
+        Wn = self.world_size
+        pipe = _Pipeline(self.device, self.side)
+        events = self._gather_deltas(plan, pipe)
         for bi, sb in enumerate(plan.s_buckets):
             q = bi % 2
-            while plan.g_buckets[gi][1] < sb.b:
-                gi += 1
-            if self.on_gpu:
-                cur.wait_event(events[gi])  # the delta buckets that cover modules [a, b) (in stream order)
-            dsts, pack, scat = self._shard_views(plan, sb)
+            pipe.wait(events[plan.g_of[sb.b - 1]])  # the delta buckets that cover modules [a, b) (in stream order)
+            dsts, owners, pack, scat = self._shard_views(plan, sb)
+            items = lambda sb=sb: self._shard_items(plan, sb, self.rank)  # noqa: E731
             if dsts and plan.sr:
-                # the own row blocks: element index r0 * in (a multiple of 8: blocks start on multiples of 8
-                # rows), the module's offset -- the bits any rank would give these rows
-                idxs, elem0s = [], []
-                for i in range(sb.a, sb.b):
-                    L = plan.arena.layers[i]
-                    r0, r1 = shard_rows(L.out_features, Wn, self.rank)
-                    if r1 > r0:
-                        idxs.append(i)
-                        elem0s.append(r0 * L.in_features)
-                self._sr_merge(plan, ("s", bi), lambda sb=sb: self._shard_items(plan, sb, self.rank), dsts, idxs, elem0s)
-            elif dsts and self.grouped:  # (no rows in the whole bucket: no plan)
-                for p, _ in plan.delta_plans(("s", bi), ops, lambda sb=sb: self._shard_items(plan, sb, self.rank),
-                                             HDP_DW_MERGE, dsts):
-                    p.run()
-            elif dsts:
-                for it in self._shard_items(plan, sb, self.rank):
-                    ops.delta_gemm(*it, HDP_DW_MERGE, it[-1].dtype == torch.bfloat16)
-            send, gath = plan.s_send[q][:sb.nbytes], plan.s_gath[q][:Wn * sb.nbytes]
-            if not self.on_gpu:
-                self._copy(pack[q])
-                self.comm.allgather_any(send, gath)
-                self._copy(scat[q])
-                continue
-            if freed[q] is not None:
-                cur.wait_event(freed[q])  # the all-gather and scatter that read this buffer pair are done
+                self._sr_merge(plan, ("s", bi), items, dsts, owners)
+            elif dsts:  # (no rows in the whole bucket: no plan)
+                self._k4(plan, ("s", bi), items, HDP_DW_MERGE, dsts)
+            pipe.acquire(q)  # the all-gather and scatter that read this buffer pair are done
             self._copy(pack[q])
-            computed = torch.cuda.Event()
-            computed.record(cur)
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(computed)
-                self.comm.allgather_any(send, gath)
+            with pipe.on_side(q):
+                self.comm.allgather_any(plan.s_send[q][:sb.nbytes], plan.s_gath[q][:Wn * sb.nbytes])
                 self._copy(scat[q])  # (the own block is already in place)
-                ev = torch.cuda.Event()
-                ev.record(self.side)
-            freed[q] = ev
-            last = ev
-        if self.on_gpu and last is not None:
-            cur.wait_event(last)
+        pipe.drain()
 
     # -- exchange = "allreduce" ----------------------------------------------------------
     def _allreduce(self, plan: _ArenaPlan) -> None:
-        arena, ops = plan.arena, self.ops
-        cur = torch.cuda.current_stream(self.device) if self.on_gpu else None
-        freed = [None, None]
-        last = None
+        arena = plan.arena
+        pipe = _Pipeline(self.device, self.side)
         for bi, (a, b) in enumerate(plan.a_buckets):
-            buf = plan.dw_bufs[bi % 2]
-            if self.on_gpu and freed[bi % 2] is not None:
-                cur.wait_event(freed[bi % 2])  # the merges that read this buffer are done
-            off, slots, items = 0, [], []
+            q = bi % 2
+            buf = plan.dw_bufs[q]
+            pipe.acquire(q)  # the merges that read this buffer are done
+            off, slots = 0, []
             for i in range(a, b):
                 L = arena.layers[i]
-                oa, ob = arena.offsets[i]
                 n = L.out_features * L.in_features
-                items.append((L.out_features, L.in_features, L.r, 1, arena.delta[oa:], arena.delta[ob:], 0,
-                              arena.fac[oa:], arena.fac[ob:], 0, buf[off:off + n]))
                 slots.append((L, off, n))
                 off += n
-            if self.grouped:
-                for p, _ in plan.delta_plans(("a", bi), ops, lambda items=items: items, HDP_DW_STORE,
-                                             [it[-1] for it in items]):
-                    p.run()
-            else:
-                for it in items:
-                    ops.delta_gemm(*it, HDP_DW_STORE, False)
+            dsts = [buf[o:o + n] for _, o, n in slots]
+            self._k4(plan, ("a", bi), lambda: [plan.local_item(arena, a + j, d) for j, d in enumerate(dsts)],
+                     HDP_DW_STORE, dsts)
             if self.on_gpu and self.world_size == 1:
                 # the all-reduce of one rank is the identity: the bucket's K5 follows its K4 on the
                 # same stream (a side-stream merge would only contend with the next K4 for HBM)
                 if plan.sr:
                     slots = self._sr_slots(buf, slots)
                 if slots:
-                    ops.merge_group([(L.W_res, buf[o:o + n].view_as(L.W_res)) for L, o, n in slots])
-            elif self.on_gpu:
-                computed = torch.cuda.Event()
-                computed.record(cur)
-                with torch.cuda.stream(self.side):
-                    self.side.wait_event(computed)
-                    self._exchange_merge(plan, bi, buf, off, slots)
-                    ev = torch.cuda.Event()
-                    ev.record(self.side)
-                freed[bi % 2] = ev
-                last = ev
+                    self._merge_group([(L.W_res, buf[o:o + n].view_as(L.W_res)) for L, o, n in slots])
             else:
-                self._exchange_merge(plan, bi, buf, off, slots)
-        if self.on_gpu and last is not None:
-            cur.wait_event(last)
-
+                with pipe.on_side(q):
+                    self._exchange_merge(plan, bi, buf, off, slots)
+        pipe.drain()
 
     def _exchange_merge(self, plan: _ArenaPlan, bi: int, buf: torch.Tensor, off: int, slots) -> None:
         """One bucket's exchange + merge on the current stream.
@@ -744,11 +743,7 @@ class HDPissaStep:
                 slots = self._sr_slots(src, slots)
                 if not slots:
                     return
-        if hasattr(ops, "merge_group"):  # the bucket's K5 as one launch
-            ops.merge_group([(L.W_res, src[o:o + n].view_as(L.W_res)) for L, o, n in slots])
-        else:
-            for L, o, n in slots:
-                ops.merge(L.W_res, src[o:o + n])
+        self._merge_group([(L.W_res, src[o:o + n].view_as(L.W_res)) for L, o, n in slots])
 
 
 _STEPPERS: Dict[int, HDPissaStep] = {}
@@ -765,10 +760,7 @@ def hd_pissa_step(model: nn.Module, lr: float, t: int, world_size: int, rank: in
     rounding from the float32 sum (HDPissaStep; "nearest", the default: the reference's merge)."""
     st = _STEPPERS.get(id(model))
     mgn = None if max_grad_norm is None else float(max_grad_norm)
-    seed = None
-    if merge_rounding == "stochastic":
-        from .rounding import default_sr_seed
-        seed = default_sr_seed(torch.initial_seed()) if sr_seed is None else int(sr_seed) & (2 ** 64 - 1)
+    seed = _sr_seed(merge_rounding, sr_seed)
     if st is None or st.exchange != exchange or st.max_grad_norm != mgn or st.merge_rounding != merge_rounding \
             or st.sr_seed != seed:
         st = HDPissaStep(model, world_size, rank, comm=comm, ops=ops, exchange=exchange, beta1=beta1, beta2=beta2,
