@@ -274,6 +274,104 @@ __global__ __launch_bounds__(kEwThreads) void copy_chunk_kernel(CopyGroupArgs ga
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Grouped float32 -> bf16 cast (hdp_shadow_group): the bf16 compute copy of float32 master weights
+// (compute_dtype=), refreshed after a bucket's merge in one launch instead of one copy_ per module.
+// dst[i] = f32_to_bf16(src[i]).  copy_chunk_kernel's form with the conversion between the loads and the
+// stores, 6 B per element: one flat chunk space over the items, a workgroup owns kShadowU x 256 consecutive
+// 8-element vectors at a time (two 16-byte float32 loads and one 16-byte store each), every load of the
+// chunk issued before its first store, non-temporal both ways (each byte touched once).  An item with dst
+// and src both 16-byte aligned runs as vectors, its n % 8 tail elements one per lane on its first chunk (an
+// item shorter than one vector still owns that chunk); any other item runs element by element over the
+// same chunk walk, with the same bits.
+// ---------------------------------------------------------------------------------------
+constexpr int kShadowU = 8;           // vectors per lane per chunk
+constexpr int kShadowGroupMax = 170;
+struct ShadowGroupArgs {
+  int n;
+  hdp_shadow_item it[kShadowGroupMax];
+};
+static_assert(sizeof(ShadowGroupArgs) <= 4096, "shadow group kernel arguments must stay within 4 KB");
+constexpr int64_t kShadowChunk = (int64_t)kEwThreads * kShadowU;  // vectors per chunk (8 elements each)
+
+// the split of one item (n > 0): whether it runs as vectors, how many, and the chunks it owns
+struct ShadowSplit {
+  bool vec;
+  int64_t nv, nch;
+};
+__host__ __device__ inline ShadowSplit shadow_split(const void* dst, const void* src, int64_t n) {
+  ShadowSplit s;
+  s.vec = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0;
+  if (s.vec) {
+    s.nv = n >> 3;
+    s.nch = s.nv ? (s.nv + kShadowChunk - 1) / kShadowChunk : 1;  // (tail only: still one chunk)
+  } else {
+    s.nv = 0;
+    s.nch = (n + kShadowChunk * 8 - 1) / (kShadowChunk * 8);
+  }
+  return s;
+}
+
+__global__ __launch_bounds__(kEwThreads) void shadow_chunk_kernel(ShadowGroupArgs ga) {
+  int it = 0;
+  ShadowSplit sp = shadow_split(ga.it[0].dst, ga.it[0].src, ga.it[0].n);
+  int64_t base = 0;                                     // item it owns chunks [base, base + sp.nch)
+  for (int64_t c = blockIdx.x;; c += gridDim.x) {      // c, it, base, sp: workgroup-uniform
+    while (c >= base + sp.nch) {
+      base += sp.nch;
+      if (++it == ga.n) return;
+      sp = shadow_split(ga.it[it].dst, ga.it[it].src, ga.it[it].n);
+    }
+    const int64_t n = ga.it[it].n;
+    HDP_GLOBAL uint16_t* D1 = gptr(reinterpret_cast<uint16_t*>(ga.it[it].dst));
+    const HDP_GLOBAL float* S1 = gptr(ga.it[it].src);
+    if (sp.vec) {
+      HDP_GLOBAL u32x4* D8 = reinterpret_cast<HDP_GLOBAL u32x4*>(D1);
+      const HDP_GLOBAL f32x4* S4 = reinterpret_cast<const HDP_GLOBAL f32x4*>(S1);
+      const int64_t v0 = (c - base) * kShadowChunk + threadIdx.x;
+      f32x4 x0[kShadowU], x1[kShadowU];
+#pragma unroll
+      for (int u = 0; u < kShadowU; ++u) {
+        const int64_t i = v0 + u * kEwThreads;
+        if (i < sp.nv) {
+          x0[u] = __builtin_nontemporal_load(S4 + 2 * i);
+          x1[u] = __builtin_nontemporal_load(S4 + 2 * i + 1);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kShadowU; ++u) {
+        const int64_t i = v0 + u * kEwThreads;
+        if (i < sp.nv) {
+          const u32x4 o{(uint32_t)f32_to_bf16(x0[u][0]) | ((uint32_t)f32_to_bf16(x0[u][1]) << 16),
+                        (uint32_t)f32_to_bf16(x0[u][2]) | ((uint32_t)f32_to_bf16(x0[u][3]) << 16),
+                        (uint32_t)f32_to_bf16(x1[u][0]) | ((uint32_t)f32_to_bf16(x1[u][1]) << 16),
+                        (uint32_t)f32_to_bf16(x1[u][2]) | ((uint32_t)f32_to_bf16(x1[u][3]) << 16)};
+          __builtin_nontemporal_store(o, D8 + i);
+        }
+      }
+      if (c == base) {  // the item's first chunk: the n % 8 tail elements, one per lane
+        const int64_t j = 8 * sp.nv + threadIdx.x;
+        if (threadIdx.x < 8 && j < n) D1[j] = f32_to_bf16(S1[j]);
+      }
+    } else {
+      const int64_t e0 = (c - base) * kShadowChunk * 8 + threadIdx.x;
+      float x[2 * kShadowU];
+      for (int64_t o = 0; o < kShadowChunk * 8; o += (int64_t)kEwThreads * 2 * kShadowU) {
+#pragma unroll
+        for (int u = 0; u < 2 * kShadowU; ++u) {
+          const int64_t i = e0 + o + u * kEwThreads;
+          if (i < n) x[u] = S1[i];
+        }
+#pragma unroll
+        for (int u = 0; u < 2 * kShadowU; ++u) {
+          const int64_t i = e0 + o + u * kEwThreads;
+          if (i < n) D1[i] = f32_to_bf16(x[u]);
+        }
+      }
+    }
+  }
+}
+
 static int merge_chunk_launch(const MergeGroupArgs& ga, bool bf16, double bytes, hipStream_t st) {
   // the chunk the kernel walks (merge_chunk_kernel<BF>'s U): the grid never exceeds the chunk count
   const int64_t CH = (int64_t)kEwThreads * (bf16 ? 2 * kMergeU : kMergeU);
@@ -942,6 +1040,46 @@ extern "C" int hdp_copy_group(int n, const hdp_copy_item* items, void* stream) {
     chunks += copy_split(items[i].dst, items[i].src, items[i].bytes).nch;
     bytes += (double)items[i].bytes;
     if (++ga.n == kCopyGroupMax) {
+      const int rc = launch();
+      if (rc) return rc;
+    }
+  }
+  return launch();
+}
+
+extern "C" int hdp_shadow_group(int n, const hdp_shadow_item* items, void* stream) {
+  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "hdp_shadow_group: bad item list");
+  for (int i = 0; i < n; ++i) {  // all of it before the first launch
+    HDP_CHECK_ARG(items[i].n >= 0, "hdp_shadow_group: item %d has n < 0", i);
+    HDP_CHECK_ARG(items[i].n == 0 || (items[i].dst && items[i].src), "hdp_shadow_group: item %d has a null pointer", i);
+    HDP_CHECK_ARG(items[i].n == 0 || ((reinterpret_cast<uintptr_t>(items[i].dst) & 1u) == 0 &&
+                                      (reinterpret_cast<uintptr_t>(items[i].src) & 3u) == 0),
+                  "hdp_shadow_group: item %d: dst must be 2-byte and src 4-byte aligned", i);
+  }
+  hipStream_t st = as_stream(stream);
+  ShadowGroupArgs ga;
+  ga.n = 0;
+  double bytes = 0;
+  int64_t chunks = 0;
+  auto launch = [&]() -> int {
+    if (ga.n == 0) return HDP_OK;
+    const unsigned grid = (unsigned)(chunks < kMergeGrid ? chunks : kMergeGrid);
+    {
+      KTimer kt(K_SHADOW, st, bytes);
+      hipLaunchKernelGGL(shadow_chunk_kernel, dim3(grid), dim3(kEwThreads), 0, st, ga);
+    }
+    HDP_CHECK_LAUNCH();
+    ga.n = 0;
+    bytes = 0;
+    chunks = 0;
+    return HDP_OK;
+  };
+  for (int i = 0; i < n; ++i) {
+    if (items[i].n == 0) continue;
+    ga.it[ga.n] = items[i];
+    chunks += shadow_split(items[i].dst, items[i].src, items[i].n).nch;
+    bytes += 6.0 * (double)items[i].n;
+    if (++ga.n == kShadowGroupMax) {
       const int rc = launch();
       if (rc) return rc;
     }

@@ -52,6 +52,11 @@ class CopyItem(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
 
 
+class ShadowItem(ctypes.Structure):
+    """hdp_shadow_item (include/hdpissa.h)."""
+    _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("n", ctypes.c_int64)]
+
+
 class ClipState(ctypes.Structure):
     """hdp_clip_state (include/hdpissa.h): the 32-byte device record of one step's gradient norm."""
     _fields_ = [("sumsq", ctypes.c_double), ("norm", ctypes.c_float), ("coef", ctypes.c_float),
@@ -71,6 +76,8 @@ def clip_record(raw) -> dict:
 
 
 COPY_GROUP_MAX = 170 # non-empty items per launch of hdp_copy_group (its kernel-argument block)
+SHADOW_GROUP_MAX = 170  # non-empty items per launch of hdp_shadow_group (its kernel-argument block)
+SHADOW_CHUNK = 256 * 8 * 8  # elements one workgroup of hdp_shadow_group casts at a time
 
 
 class SvdItem(ctypes.Structure):
@@ -97,6 +104,7 @@ SIGNATURES = {
     "hdp_merge_group_sr": (_c_int, [_c_int, ctypes.POINTER(MergeSrItem), ctypes.c_uint64, _c_vp]),
     "hdp_fold_bf16": (_c_int, [_c_vp, _c_int, _c_i64, _c_vp, _c_i64, _c_vp]),
     "hdp_copy_group": (_c_int, [_c_int, ctypes.POINTER(CopyItem), _c_vp]),
+    "hdp_shadow_group": (_c_int, [_c_int, ctypes.POINTER(ShadowItem), _c_vp]),
     "hdp_adam_factors": (_c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
                                   _c_f, _c_f, _c_f, _c_int, _c_vp]),
     "hdp_grad_sumsq_workspace_bytes": (_c_sz, [_c_i64]),

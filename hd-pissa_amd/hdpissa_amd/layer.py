@@ -25,12 +25,18 @@ What changes underneath (MI355X-native):
   * dropout > 0 (train mode): the backward of a call runs the fused masked kernel at once with
     that call's (seed, offset) -- ``layer.dropout_calls`` / ``layer.last_dropout_state``, mask
     contract in ``hdpissa_amd.dropout``; the forward output and dX are untouched.
+  * compute_dtype=torch.bfloat16 on a float32 W_res (opt-in; the reference computes in the precision it
+    stores): float32 master weights with a bf16 compute copy.  ``layer.W_lp`` (a non-persistent buffer:
+    checkpoints are unchanged) holds bf16(W_res); the base GEMMs of forward and backward read it -- y and
+    dX are bf16 GEMMs on bf16(x) -- and the probe takes the bf16 activations through its bf16 paths, while
+    the step keeps merging into the float32 W_res and refreshes the copy (``refresh_shadow``, HDPissaStep).
 """
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import os
+import weakref
 
 import numpy as np
 
@@ -97,6 +103,12 @@ class FactorArena:
                 self.fac_all[i, ob:ob + out * r].view(out, r).copy_(B_all[i])
             L._bind(self, oa, ob)
         self.probe_queue = ProbeQueue(layers[0].ops if layers else None)
+        # compute_dtype=: the last float32 activation a shadowed layer of this arena cast to bf16, as
+        # (weak reference to x, x._version, shape, strides, bf16 x) -- q / k / v and gate / up are handed
+        # one x, and K2's shared-X sets are formed by pointer, so they must get one bf16 tensor.  At most
+        # one activation is held; cleared when a backward pass starts or ends and at step()
+        self.cast_cache = None
+        self.probe_queue.arena = self
         self.comm = None  # the communicator of the sharded init, if any (replace_with_custom_layer)
 
     def views(self, buf: torch.Tensor, idx: int):
@@ -151,6 +163,7 @@ class ProbeQueue:
         self._nq = {}             # x dtype -> native queue (hdpissa_amd._C.ProbeQueue)
         self._native_dtype = None  # dtype of the native queue holding pending modules, if any
         self._nmax = int(os.environ.get("HDP_PROBE_GROUP", "256"))
+        self.arena = None  # the FactorArena this queue serves (set by it): its cast cache ends with a backward pass
 
     def _max_group(self) -> int:
         if self._max is None:
@@ -267,6 +280,8 @@ class ProbeQueue:
 
     def _end_of_backward(self) -> None:
         self.flush()
+        if self.arena is not None:
+            self.arena.cast_cache = None
 
     def flush(self) -> None:
         self._flush_native()
@@ -311,6 +326,13 @@ class _ProbeLinearFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W_res, bias, A, B, layer):
+        # compute_dtype=: the bf16 copy of W_res if the layer keeps one (then x, y, dX and the probe's
+        # activations are bf16: x itself, or its bf16 cast, is what backward keeps)
+        lp = layer._shadow()
+        ctx.lp = lp
+        if lp is not None:
+            ctx.x_dtype = x.dtype
+            x = layer._cast_x(x)
         ctx.save_for_backward(x)
         ctx.layer = layer
         p = layer.dropout_rate
@@ -323,12 +345,23 @@ class _ProbeLinearFn(torch.autograd.Function):
             ctx.dropout = (float(p), seed, offset)
         else:
             ctx.dropout = None
+        if lp is not None:
+            return F.linear(x, lp, layer._bias_shadow())
         return F.linear(x, W_res, bias)
 
     @staticmethod
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
         layer = ctx.layer
+        lp = ctx.lp
+        if lp is not None:
+            layer._arena.cast_cache = None  # (the forward passes are over: nothing holds the last cast)
+            dx = None
+            if ctx.needs_input_grad[0]:
+                gy_lp = gy if gy.dtype == torch.bfloat16 else gy.to(torch.bfloat16)
+                dx = gy_lp.matmul(lp).to(ctx.x_dtype)
+            layer._probe_backward(x, gy, ctx.dropout)
+            return dx, None, None, None, None, None
         dx = gy.matmul(layer.W_res) if ctx.needs_input_grad[0] else None
         layer._probe_backward(x, gy, ctx.dropout)
         return dx, None, None, None, None, None
@@ -339,9 +372,10 @@ class CustomLinearLayer(nn.Module):
 
     def __init__(self, original_linear: nn.Linear, name: str, device_id: int, world_size: int,
                  ranks_per_gpu: Optional[int] = None, alpha: float = 0.0, dropout: float = 0.0, *,
-                 ops=None, residual: bool = False, _factors: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                 _defer_arena: bool = False):
+                 ops=None, residual: bool = False, compute_dtype: Optional[torch.dtype] = None,
+                 _factors: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, _defer_arena: bool = False):
         super().__init__()
+        _check_compute_dtype(compute_dtype, original_linear.weight.dtype)
         self.residual = bool(residual)  # opt-in PiSSA-residual storage (see make_residual)
         self.name = name
         self.in_features = original_linear.in_features
@@ -372,6 +406,16 @@ class CustomLinearLayer(nn.Module):
         self.B = nn.Parameter(B_all[device_id].clone())
         self.register_buffer("W_res", W.clone().detach())                   # hp:129 (W, not W - BA)
         self.bias = original_linear.bias if original_linear.bias is not None else None  # hp:131-134
+        # compute_dtype=bfloat16 on a float32 W_res: W_lp = bf16(W_res), read by the base GEMMs; not in the
+        # state dict.  None when the mode is off (bf16 on a bf16 W_res: nothing to copy, the plain path)
+        self.compute_dtype = compute_dtype
+        shadow = compute_dtype is not None and W.dtype == torch.float32
+        self.register_buffer("W_lp", torch.empty_like(self.W_res, dtype=torch.bfloat16) if shadow else None,
+                             persistent=False)
+        self._shadow_version = None
+        self._bias_lp, self._bias_lp_version = None, None
+        if shadow:
+            self.refresh_shadow()
         self._arena: Optional[FactorArena] = None
         if not _defer_arena:
             FactorArena([self], [(A_all, B_all)], world_size, device_id, W.device)
@@ -406,12 +450,78 @@ class CustomLinearLayer(nn.Module):
         self.m_B = arena.m[ob:ob + out * r].view(out, r)
         self.v_B = arena.v[ob:ob + out * r].view(out, r)
 
+    # -- compute_dtype: the bf16 copy of a float32 W_res -------------------------------------
+    def refresh_shadow(self) -> None:
+        """W_lp <- bf16(W_res) (round to nearest even) on the current stream: the grouped cast kernel
+        (``shadow_group``), or ``copy_`` where the op set has none.  The forward calls it when W_res's
+        version counter moved (``copy_``, ``load_state_dict``, ``load_hdpissa_state``) and the optimizer
+        step refreshes the copies itself; after a write the counter does not see (``.data``, raw
+        pointers) the caller calls it.  A no-op without a copy."""
+        bufs = self._buffers
+        W, lp = bufs["W_res"], bufs.get("W_lp")
+        if lp is None:
+            return
+        with torch.no_grad():
+            f = getattr(self.ops, "shadow_group", None)
+            if f is not None:
+                f([(lp, W)])
+            else:
+                lp.copy_(W)
+        self._shadow_version = W._version
+
+    def _shadow(self) -> Optional[torch.Tensor]:
+        """The current bf16 copy of W_res, or None if the layer keeps none.  A W_res that is no longer
+        float32 (``model.to(torch.bfloat16)``) drops the copy for good: the layer takes the plain path."""
+        bufs = self._buffers
+        lp = bufs.get("W_lp")
+        if lp is None:
+            return None
+        W = bufs["W_res"]
+        if W.dtype != torch.float32:
+            self.W_lp, self.compute_dtype = None, None
+            return None
+        if lp.dtype != torch.bfloat16 or lp.device != W.device:  # (model.float() / a move widened or left it)
+            self.W_lp = lp = torch.empty_like(W, dtype=torch.bfloat16)
+            self._shadow_version = None
+        if self._shadow_version != W._version:
+            self.refresh_shadow()
+        return lp
+
+    def _bias_shadow(self) -> Optional[torch.Tensor]:
+        """bf16(bias), cast once and again when the bias is written."""
+        b = self.bias
+        if b is None:
+            return None
+        lp = self._bias_lp
+        if lp is None or self._bias_lp_version != b._version or lp.device != b.device:
+            lp = self._bias_lp = b.detach().to(torch.bfloat16)
+            self._bias_lp_version = b._version
+        return lp
+
+    def _cast_x(self, x: torch.Tensor) -> torch.Tensor:
+        """x as bf16: x itself, the arena's cached cast if the previous shadowed layer was handed this very
+        tensor (same object, version, shape and strides), else a fresh cast that replaces the cache."""
+        if x.dtype == torch.bfloat16:
+            return x
+        arena = self._arena
+        c = arena.cast_cache if arena is not None else None
+        if c is not None and c[0]() is x and c[1] == x._version and c[2] == x.shape and c[3] == x.stride():
+            return c[4]
+        x_lp = x.detach().to(torch.bfloat16)
+        if arena is not None:
+            arena.cast_cache = (weakref.ref(x), x._version, x.shape, x.stride(), x_lp)
+        return x_lp
+
     # -- forward / backward ----------------------------------------------------------------
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if torch.is_grad_enabled() and (self.A.requires_grad or self.B.requires_grad):
             y = _ProbeLinearFn.apply(x, self.W_res, self.bias, self.A, self.B, self)
         else:
-            y = F.linear(x, self.W_res, self.bias)
+            lp = self._shadow()
+            if lp is not None:  # the same bf16 GEMM as under autograd
+                y = F.linear(self._cast_x(x), lp, self._bias_shadow())
+            else:
+                y = F.linear(x, self.W_res, self.bias)
         if self.residual:
             # the principal components live in the frozen factors: y += (x32 A_all^T) B_cat^T
             # (fp32, cast back like the reference's adapter term, hp:139); constant factors, so
@@ -563,6 +673,16 @@ class CustomLinearLayer(nn.Module):
                 f"in_features={self.in_features}, out_features={self.out_features})")
 
 
+def _check_compute_dtype(compute_dtype, w_dtype) -> None:
+    """compute_dtype: None, or torch.bfloat16 on a float32 W (a bf16 copy is kept) or on a bf16 W (no-op)."""
+    if compute_dtype is None:
+        return
+    if compute_dtype != torch.bfloat16:
+        raise ValueError(f"compute_dtype must be None or torch.bfloat16, got {compute_dtype!r}")
+    if w_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"compute_dtype=torch.bfloat16 needs a float32 (or bfloat16) weight, got {w_dtype}")
+
+
 def _find_targets(model: nn.Module, target_modules: Sequence[str]) -> List[Tuple[str, nn.Linear]]:
     """hp:151-153: substring match on named_modules(), nn.Linear only, first target wins."""
     found = []
@@ -623,21 +743,28 @@ def make_residual(layers: Sequence["CustomLinearLayer"]) -> None:
             else:
                 for it in group:
                     ops.delta_gemm(*it, HDP_DW_MERGE, False)
+    for L in layers:  # K4 wrote W_res through its pointer: the bf16 copies follow
+        L.refresh_shadow()
 
 
 def replace_with_custom_layer(model: nn.Module, target_modules: Sequence[str], rank: int, world_size: int,
                               ranks_per_gpu: Optional[int] = None, alpha: float = 0.0, dropout: float = 0.0, *,
-                              comm=None, ops=None, residual: bool = False) -> List[CustomLinearLayer]:
+                              comm=None, ops=None, residual: bool = False,
+                              compute_dtype: Optional[torch.dtype] = None) -> List[CustomLinearLayer]:
     """hp:150-156, MI355X-native.
 
     All targeted layers share one FactorArena.  With ``world_size > 1`` and an initialised
     torch.distributed group (or an explicit ``comm``), the top-k SVDs are sharded: module j
     is decomposed by rank ``j % world_size`` and its (A_all, B_all) broadcast to every rank.
-    Returns the new layers in module order.
+    Returns the new layers in module order.  ``compute_dtype=torch.bfloat16``: float32 targets keep a bf16
+    copy of W_res that their base GEMMs read (CustomLinearLayer; run the model under
+    ``torch.autocast(dtype=torch.bfloat16)``).
     """
     targets = _find_targets(model, target_modules)
     if not targets:
         return []
+    for _, module in targets:
+        _check_compute_dtype(compute_dtype, module.weight.dtype)
     _alpha_eff(alpha, ranks_per_gpu)
     r = int(ranks_per_gpu)
     if ops is None:
@@ -680,8 +807,8 @@ def replace_with_custom_layer(model: nn.Module, target_modules: Sequence[str], r
         factors.append((A_all, B_all))
     layers = []
     for (name, module), fac in zip(targets, factors):
-        layer = CustomLinearLayer(module, name, rank, world_size, r, alpha, dropout, ops=ops, _factors=fac,
-                                  _defer_arena=True)
+        layer = CustomLinearLayer(module, name, rank, world_size, r, alpha, dropout, ops=ops,
+                                  compute_dtype=compute_dtype, _factors=fac, _defer_arena=True)
         setattr(get_parent_module(model, name), name.split(".")[-1], layer)
         layers.append(layer)
     arena = FactorArena(layers, factors, world_size, rank, device)

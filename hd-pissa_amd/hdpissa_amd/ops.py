@@ -416,6 +416,24 @@ class HipOps:
             arr[i].dst, arr[i].src, arr[i].bytes = dst.data_ptr(), src.data_ptr(), nb
         check(lib().hdp_copy_group(len(pairs), arr, _stream()), "hdp_copy_group")
 
+    def shadow_group(self, pairs) -> None:
+        """dst <- bf16(src), round to nearest even, for many contiguous ``(dst bfloat16, src float32)`` pairs of
+        equal numel in one launch per ``_lib.SHADOW_GROUP_MAX`` pairs: the bf16 compute copies of float32
+        master weights (hdp_shadow_group; host replica of the conversion: rounding.rne_bf16_bits)."""
+        from ._lib import ShadowItem
+        if not pairs:
+            return
+        arr = (ShadowItem * len(pairs))()
+        for i, (dst, src) in enumerate(pairs):
+            _need_gpu(dst, src)
+            _f32(src)
+            if dst.dtype != torch.bfloat16:
+                raise TypeError(f"shadow_group: dst must be bfloat16, got {dst.dtype}")
+            if dst.numel() != src.numel() or not dst.is_contiguous() or not src.is_contiguous():
+                raise ValueError("shadow_group: dst and src must be contiguous with equal sizes")
+            arr[i].dst, arr[i].src, arr[i].n = dst.data_ptr(), src.data_ptr(), dst.numel()
+        check(lib().hdp_shadow_group(len(pairs), arr, _stream()), "hdp_shadow_group")
+
     def fold_bf16(self, parts: torch.Tensor, out: torch.Tensor) -> None:
         """Rank-ordered bf16 fold (hp:389-392 rounding order): parts [nparts, n] float32 (rank i's
         term -bracket_i in row i), out [n] bfloat16 = bf16(...bf16(bf16(0 + p0) + p1)... + p_last)."""

@@ -50,6 +50,15 @@ float32 all-reduce instead of the rank-ordered fold.  The random bits depend on 
 only, so every rank -- and under "shard" whichever rank merges a row -- writes the same W.  float32 modules
 take exactly the launches they always took.
 
+Opt-in, off by default (``compute_dtype=torch.bfloat16`` on the layers; the reference computes in the precision
+it stores): float32 master weights with a bf16 compute copy.  When ``step()`` returns, every layer that keeps a
+copy has W_lp == bf16(W_res) element for element, in stream order on the current stream, on every rank, under
+every exchange, with and without ``max_grad_norm`` and after a skipped step: one grouped cast launch
+(hdp_shadow_group) per K4 / K5 launch site and bucket over that bucket's shadowed float32 modules -- gather:
+after the bucket's MERGE on the main stream; allreduce: after the bucket's K5 on the stream that ran it; shard:
+after the bucket's scatter on the side stream (the own rows are ordered by the hand-over event, the end by the
+drain).  Buckets without such modules, and steppers without any, launch nothing.
+
 Semantics kept from the reference: Adam without weight decay, bias correction with the
 post-increment t (hp:350), A and B never updated (hp:375-376; the deltas are recomputed
 against the *initial* factors every step), grads scaled x1e16 (hp:356-357), bf16 models
@@ -150,6 +159,10 @@ class _ArenaPlan:
         if exchange == "allreduce":
             self._build_allreduce(bucket_bytes)
         self.plans: Dict[tuple, list] = {}   # grouped K4 launches, built on first use
+        # compute_dtype=: layers of this arena keep a bf16 copy of a float32 W_res; per launch site the
+        # (pointers, (W_lp, W_res) pairs, layers) of its shadowed modules, cached while no buffer moved
+        self.shadowed = any(L._buffers.get("W_lp") is not None for L in arena.layers)
+        self.shadow_pairs: Dict[object, tuple] = {}
 
     def _build_sr(self) -> None:
         arena = self.arena
@@ -378,6 +391,8 @@ class HDPissaStep:
         # the bucket's K5 and the shard exchange's pack / scatter as one launch where the op set has them
         self._merge_group = getattr(ops, "merge_group", None) or (lambda pairs: [ops.merge(W, dW) for W, dW in pairs])
         self._copy = getattr(ops, "copy_group", None) or _copy_pairs
+        # the bf16 copies of a bucket's float32 modules as one launch (compute_dtype=; never called without one)
+        self._shadow_group = getattr(ops, "shadow_group", None) or _copy_pairs
         # global gradient-norm clipping + non-finite-step skip (off by default: nothing below is built or
         # launched then).  c > 0; math.inf = measure and guard only
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
@@ -451,6 +466,7 @@ class HDPissaStep:
         with torch.no_grad():
             for plan in self.plans:
                 plan.arena.probe_queue.flush()  # grads of deferred probe launches first
+                plan.arena.cast_cache = None
             chk = getattr(self.ops, "probe_errors", None)
             if chk is not None and chk():
                 # a probe launch that has completed reported a failed hand-off: its gradients are
@@ -486,6 +502,7 @@ class HDPissaStep:
             for p, _ in fused:
                 p.run_adam(arena.grad, arena.m, arena.v, arena.delta, t, lr, self.beta1, self.beta2, self.eps,
                            zero_grad=True, **kw)
+            self._shadow(plan, "g1", arena.layers)  # (fused plans merge bf16 W only: nothing to cast)
             return
         ops.adam(arena.grad, arena.m, arena.v, arena.delta, t, lr, self.beta1, self.beta2, self.eps, zero_grad=True,
                  **kw)
@@ -532,6 +549,27 @@ class HDPissaStep:
         """World size 1: every module's merge on this rank's own deltas."""
         arena = plan.arena
         return self._k4(plan, "g1", lambda: self._items_w1(arena), HDP_DW_MERGE, [L.W_res for L in arena.layers], run)
+
+    # -- compute_dtype: the bf16 copies of float32 W_res ---------------------------------
+    def _shadow(self, plan: _ArenaPlan, key, layers) -> None:
+        """W_lp <- bf16(W_res) for the shadowed float32 modules among ``layers`` (one launch site's bucket):
+        one shadow_group on the current stream, after the writes to their W_res enqueued on it; nothing
+        where the bucket has no such module.  The pair list is cached under ``key`` while no buffer moved."""
+        if not plan.shadowed:
+            return
+        ptrs = tuple((L._buffers["W_res"].data_ptr(), 0 if L._buffers.get("W_lp") is None else L._buffers["W_lp"].data_ptr())
+                     for L in layers)
+        cache = plan.shadow_pairs.get(key)
+        if cache is None or cache[0] != ptrs:
+            sh = [L for L in layers if L._buffers.get("W_lp") is not None and L._buffers["W_res"].dtype == torch.float32
+                  and L._buffers["W_lp"].dtype == torch.bfloat16]
+            cache = plan.shadow_pairs[key] = (ptrs, [(L._buffers["W_lp"], L._buffers["W_res"]) for L in sh], sh)
+        _, pairs, sh = cache
+        if not pairs:
+            return
+        self._shadow_group(pairs)
+        for L, (_, W) in zip(sh, pairs):
+            L._shadow_version = W._version
 
     # -- merge_rounding = "stochastic" ---------------------------------------------------
     def _sr_offset(self, L) -> int:
@@ -609,6 +647,7 @@ class HDPissaStep:
                 self._sr_merge(plan, "g1", lambda: self._items_w1(plan.arena), [L.W_res for L in layers], layers)
             else:
                 self._k4_w1(plan)
+            self._shadow(plan, "g1", layers)
             return
         pipe = _Pipeline(self.device, self.side)
         events = self._gather_deltas(plan, pipe)
@@ -620,6 +659,7 @@ class HDPissaStep:
                 self._sr_merge(plan, ("g", bi), items, dsts, layers[a:b])
             else:
                 self._k4(plan, ("g", bi), items, HDP_DW_MERGE, dsts)
+            self._shadow(plan, ("g", bi), layers[a:b])
 
     def _gather_deltas(self, plan: _ArenaPlan, pipe: _Pipeline) -> list:
         """The bucketed all-gather of the deltas into ``delta_all`` (on the side stream on the GPU);
@@ -685,6 +725,7 @@ class HDPissaStep:
             with pipe.on_side(q):
                 self.comm.allgather_any(plan.s_send[q][:sb.nbytes], plan.s_gath[q][:Wn * sb.nbytes])
                 self._copy(scat[q])  # (the own block is already in place)
+                self._shadow(plan, ("s", bi), plan.arena.layers[sb.a:sb.b])  # (own rows: on_side's ready event)
         pipe.drain()
 
     # -- exchange = "allreduce" ----------------------------------------------------------
@@ -711,9 +752,11 @@ class HDPissaStep:
                     slots = self._sr_slots(buf, slots)
                 if slots:
                     self._merge_group([(L.W_res, buf[o:o + n].view_as(L.W_res)) for L, o, n in slots])
+                self._shadow(plan, ("a", bi), arena.layers[a:b])
             else:
                 with pipe.on_side(q):
                     self._exchange_merge(plan, bi, buf, off, slots)
+                    self._shadow(plan, ("a", bi), arena.layers[a:b])
         pipe.drain()
 
     def _exchange_merge(self, plan: _ArenaPlan, bi: int, buf: torch.Tensor, off: int, slots) -> None:

@@ -22,6 +22,11 @@ synchronisation per optimizer step.
 Added (opt-in, ``merge_rounding="stochastic"``, ``sr_seed=``; the reference rounds to nearest): bf16 weights
 take the step's update by stochastic rounding from the float32 sum (HDPissaStep).  Nothing is added to the
 checkpoint: the rounding stream is a function of ``t`` and ``sr_seed``.
+
+Added (opt-in, ``compute_dtype=torch.bfloat16``; the reference computes in the precision it stores): the model
+forward of every micro-batch runs under ``torch.autocast(dtype=compute_dtype)``.  The adapter layers are
+configured by ``replace_with_custom_layer(compute_dtype=)``: float32 master weights, a bf16 copy for the base
+GEMMs, kept current by the step.
 """
 from __future__ import annotations
 
@@ -41,7 +46,10 @@ class HDPissaTrainer:
                  schedule: str = "cosine", exchange: str = "gather", loss_sync: str = "step", comm=None, ops=None,
                  beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                  max_grad_norm: Optional[float] = None, merge_rounding: str = "nearest",
-                 sr_seed: Optional[int] = None):
+                 sr_seed: Optional[int] = None, compute_dtype: Optional[torch.dtype] = None):
+        if compute_dtype not in (None, torch.bfloat16):
+            raise ValueError(f"compute_dtype must be None or torch.bfloat16, got {compute_dtype!r}")
+        self.compute_dtype = compute_dtype
         if loss_sync not in ("step", "micro"):
             raise ValueError("loss_sync must be 'step' or 'micro'")
         if accumulation_steps < 1:
@@ -82,7 +90,11 @@ class HDPissaTrainer:
         input_ids = batch["input_ids"].to(dev, non_blocking=True)
         attention_mask = batch["attention_mask"].to(dev, non_blocking=True)
         labels = batch["labels"].to(dev, non_blocking=True)
-        outputs = self.model(input_ids=input_ids, attention_mask=attention_mask, labels=labels)
+        if self.compute_dtype is not None:
+            with torch.autocast(dev.type, dtype=self.compute_dtype):
+                outputs = self.model(input_ids=input_ids, attention_mask=attention_mask, labels=labels)
+        else:
+            outputs = self.model(input_ids=input_ids, attention_mask=attention_mask, labels=labels)
         loss = outputs.loss / float(self.accumulation_steps)
         if self.loss_sync == "micro":
             avg = self._reduce(loss.detach().clone()) / self.world_size

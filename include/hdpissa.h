@@ -132,6 +132,26 @@ typedef struct {
 } hdp_copy_item;
 int hdp_copy_group(int n, const hdp_copy_item* items, void* stream);
 
+/* Grouped float32 -> bf16 cast -- the bf16 compute copy of float32 master weights (compute_dtype=; the
+ * reference has no counterpart: it computes in the precision W_res is stored in).  The optimizer step keeps
+ * a bf16 copy of every float32 W_res that the base GEMMs read, refreshed after each bucket's merge in one
+ * launch per 170 non-empty items (what fits the kernel-argument block) instead of one cast per module.
+ *   dst[i] = bf16(src[i])  for i in [0, n), for every item; n == 0 items are skipped.
+ * Round to nearest even: a carry at the top of the range gives +-inf, subnormals and signed zeros are
+ * kept, NaN stays NaN (quiet; the sign and the upper payload bits kept) -- hdpissa_amd/rounding.py's
+ * rne_bf16_bits is the host replica.  Any n >= 0 and any alignment (dst 2-byte, src 4-byte): an item with
+ * dst and src both 16-byte aligned moves as 8-element vectors with an element-wise n % 8 tail, any other
+ * item element by element, with the same bits; nothing outside [dst, dst + n) is written and nothing
+ * outside [src, src + n) is read.  Ranges of one call must not overlap each other's dst (not checked).
+ * items is a HOST array read during the call; n < 0 or a null pointer with n > 0 is HDP_EINVAL before
+ * anything is launched. */
+typedef struct {
+  void* dst;         /* n bf16 */
+  const float* src;  /* n float32 */
+  int64_t n;
+} hdp_shadow_item;
+int hdp_shadow_group(int n, const hdp_shadow_item* items, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * K3 Adam-on-factors -- replaces hp:356-373 for a flat arena of n float32 factor entries
  * (all modules' A-side and B-side concatenated).  Per element:

@@ -5,10 +5,14 @@ drop-in CustomLinearLayer, trained by HDPissaTrainer on synthetic instruction mi
 to the longest sample), accumulation 64 // 8 = 8 micro-batches per optimizer step (run.sh).
 
   python tools/e2e_train.py [--model llama2-7b|mistral-7b|llama2-13b] [--layers N] [--steps 2] [--warmup 1]
-                            [--dtype float32|bfloat16] [--ref]
+                            [--dtype float32|bfloat16] [--compute-dtype bfloat16] [--ref]
 
 Prints one JSON line: train tokens/s of the whole step (HF forward + backward through the base
 model, the K2 probes, and the HD-PiSSA step), and the share of the step spent in the hot path.
+--compute-dtype bfloat16 (with --dtype float32): float32 master weights, the layers' bf16 copies for the
+base GEMMs, the model forward under autocast (HDPissaTrainer(compute_dtype=)).  The hot path's share is the
+device time of the library's own kernels (hdp_timing_*: probes, Adam, K4 / K5, the bf16 cast) over one extra
+step run after the timed ones, against that step's wall time.
 --ref also times the reference's own layer (hp:136-140: the out x in product B A materialised,
 the extra fp32 GEMMs in forward and backward) and its step block (hp:352-398) in torch on the
 same GPU, same model and batches.  Measurement tool: not part of the package.
@@ -106,6 +110,8 @@ def main():
     ap.add_argument("--micro", type=int, default=8)
     ap.add_argument("--model", default="llama2-7b", choices=sorted(MODELS))
     ap.add_argument("--dtype", default=None, choices=["float32", "bfloat16"], help="default: the config's own")
+    ap.add_argument("--compute-dtype", default=None, choices=["bfloat16"],
+                    help="bf16 compute copies of float32 weights, forward under autocast")
     ap.add_argument("--ref", action="store_true")
     args = ap.parse_args()
     import transformers
@@ -129,11 +135,12 @@ def main():
         p.requires_grad = False
     t_model = time.time() - t0
     t0 = time.time()
-    layers = replace_with_custom_layer(model, TARGETS, 0, 1, mc["r"], mc["alpha"])
+    cd = getattr(torch, args.compute_dtype) if args.compute_dtype else None
+    layers = replace_with_custom_layer(model, TARGETS, 0, 1, mc["r"], mc["alpha"], compute_dtype=cd)
     torch.cuda.synchronize()
     t_init = time.time() - t0
-    bs = batches((args.warmup + args.steps) * args.micro, 2, cfg.vocab_size, 42)
-    tr = HDPissaTrainer(model, 1, 0, 2e-5, 1000, args.micro, warmup_ratio=0.03, loss_sync="step")
+    bs = batches((args.warmup + args.steps + 1) * args.micro, 2, cfg.vocab_size, 42)
+    tr = HDPissaTrainer(model, 1, 0, 2e-5, 1000, args.micro, warmup_ratio=0.03, loss_sync="step", compute_dtype=cd)
 
     def run(step_fn, micro_fn, n_steps, it):
         tok = 0
@@ -164,6 +171,21 @@ def main():
                value=round(tok / el, 1), unit="tokens/s", steps=args.steps, micro_batches_per_step=args.micro,
                ms_per_step=round(1e3 * el / args.steps, 1), model_build_s=round(t_model, 1), svd_init_s=round(t_init, 1),
                loss=tr.loss_list[-args.steps:])
+    if cd is not None:
+        res["compute_dtype"] = args.compute_dtype
+    # the hot path's share: one more step with the library's per-kernel event timing on
+    from hdpissa_amd._lib import kernel_timing
+    kernel_timing(enable=True, reset=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    run(lambda: None, micro_ours, 1, it)
+    torch.cuda.synchronize()
+    el_hot = time.perf_counter() - t0
+    kt = kernel_timing(enable=False, reset=True)
+    hot_ms = sum(k["total_ms"] for k in kt.values())
+    res["hot_path_ms_per_step"] = round(hot_ms, 2)
+    res["hot_path_share"] = round(hot_ms / (1e3 * el_hot), 4)
+    res["hot_path_kernels_ms"] = {n: round(k["total_ms"], 2) for n, k in sorted(kt.items())}
     if args.ref:
         # the reference's layer + step on the same model, factors and batches
         for name, L in custom_layers(model):

@@ -1,6 +1,7 @@
 """What HDPissaStep launches, in order (comparison tool, not part of the library).
 
   python tools/step_trace.py [--device cpu|cuda] [--summary] [--only SUBSTRING] [--out FILE]
+                             [--compute-dtype bfloat16]
 
 Wraps an op set and a communicator in a recording proxy and drives the stepper through a matrix of
 configurations -- the three exchanges, world sizes, dtypes, merge roundings, gradient clipping, bucket bounds,
@@ -17,6 +18,9 @@ irrelevant, only the calls are recorded.
 --device cpu   the op sets of the host tests (CpuOps + the stochastic-rounding and clip test op sets).
 --device cuda  HipOps; every line carries the current stream (main / side), and Event.record / Stream.wait_event
                are logged (patched inside this tool only) with the event's index in order of first use.
+--compute-dtype bfloat16   another axis, off by default (the default matrix and its bytes stay): the layers keep
+               bf16 copies of their float32 W_res (named L<j>) and the trace gains the step's shadow_group calls;
+               configuration names end in -cdbfloat16; all-bf16 configurations are left out (nothing to copy).
 --summary      one line per configuration: name, line count, SHA-1 of its lines (tests/golden/step_trace_cpu.txt).
 
 Two commits that launch the same things print the same bytes:
@@ -134,13 +138,18 @@ class EchoComm:
         return None
 
 
-def cpu_ops():
+def cpu_ops(shadow=False):
     from test_clip_host import ClipCpuOps
     from test_sr_host import SrCpuOps
 
     class TraceCpuOps(ClipCpuOps, SrCpuOps):
         name = "cpu-test-trace"
-    return TraceCpuOps()
+
+    class ShadowTraceCpuOps(TraceCpuOps):
+        def shadow_group(self, pairs):
+            for dst, src in pairs:
+                dst.copy_(src)
+    return ShadowTraceCpuOps() if shadow else TraceCpuOps()
 
 
 def grads(L, j, rank, step):
@@ -148,7 +157,7 @@ def grads(L, j, rank, step):
     return torch.randn(L.A.shape, generator=g) * 1e-14, torch.randn(L.B.shape, generator=g) * 1e-14
 
 
-def configs(device):
+def configs(device, compute_dtype=None):
     """(name, settings) of every configuration of the matrix, in a fixed order."""
     out = []
     if device == "cpu":
@@ -176,6 +185,12 @@ def configs(device):
     for c in out:
         c["name"] = "%s-w%dr%d-%s-%s-clip%s-bb%s-g%s-a%d" % (
             c["exchange"], c["wn"], c["rank"], c["dts"], c["rounding"], c["clip"], c["bucket"], c["grouped"], c["arenas"])
+        c["compute_dtype"] = None
+    if compute_dtype is not None:
+        out = [c for c in out if c["dts"] != "bf16"]
+        for c in out:
+            c["compute_dtype"] = compute_dtype
+            c["name"] += "-cd" + compute_dtype
     return out
 
 
@@ -183,6 +198,7 @@ def name_buffers(rec, st, layers):
     rec.bufs = []
     for j, L in enumerate(layers):
         rec.name("W%d" % j, L.W_res)
+        rec.name("L%d" % j, getattr(L, "W_lp", None))
     for k, plan in enumerate(st.plans):
         a, pre = plan.arena, "a%d." % k
         for attr in ("grad", "m", "v", "delta", "fac", "fac_all"):
@@ -206,7 +222,7 @@ def run_config(c, device):
         from hdpissa_amd.ops import default_ops
         real, shapes = default_ops(), GPU_SHAPES
     else:
-        real, shapes = cpu_ops(), CPU_SHAPES
+        real, shapes = cpu_ops(c["compute_dtype"] is not None), CPU_SHAPES
     model = nn.Module()
     g = torch.Generator().manual_seed(5)
     for name, (out, inn), dt in zip(NAMES, shapes, DTYPES[c["dts"]]):
@@ -217,7 +233,8 @@ def run_config(c, device):
     groups = [NAMES] if c["arenas"] == 1 else [NAMES[:2], NAMES[2:]]
     layers = []
     for names in groups:  # (no communicator: every simulated rank decomposes every module itself)
-        layers += replace_with_custom_layer(model, names, c["rank"], c["wn"], c["r"], 16.0, ops=real)
+        ckw = {} if c["compute_dtype"] is None else {"compute_dtype": getattr(torch, c["compute_dtype"])}
+        layers += replace_with_custom_layer(model, names, c["rank"], c["wn"], c["r"], 16.0, ops=real, **ckw)
     old = os.environ.get("HDP_DELTA_GROUPED")
     os.environ["HDP_DELTA_GROUPED"] = c["grouped"]
     try:
@@ -249,6 +266,8 @@ def run_config(c, device):
         step(3)
         rec.lines.append("# W1 moved")
         layers[1].W_res = layers[1].W_res.clone()
+        if getattr(layers[1], "W_lp", None) is not None:
+            layers[1].refresh_shadow()  # (a W_res replaced by hand: the caller's refresh)
         step(4)
         if device == "cuda":
             torch.cuda.synchronize()
@@ -285,10 +304,10 @@ def patched_events(rec, st):
         torch.cuda.Event.record, torch.cuda.Stream.wait_event = rec_orig, wait_orig
 
 
-def run_matrix(device="cpu", only=None, progress=False):
+def run_matrix(device="cpu", only=None, progress=False, compute_dtype=None):
     """[(name, lines, unnamed tensors)] of every configuration (whose name contains ``only``)."""
     out = []
-    for c in configs(device):
+    for c in configs(device, compute_dtype):
         if only and only not in c["name"]:
             continue
         lines, unnamed = run_config(c, device)
@@ -310,10 +329,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--summary-out", default=None, help="also write the --summary form to this file")
     ap.add_argument("--progress", action="store_true", help="name every finished configuration on stderr")
+    ap.add_argument("--compute-dtype", default=None, choices=["bfloat16"],
+                    help="the matrix again with bf16 compute copies of the float32 modules (names end in -cd<dtype>)")
     args = ap.parse_args()
     if args.device == "cuda" and not torch.cuda.is_available():
         raise SystemExit("--device cuda needs a HIP device")
-    res = run_matrix(args.device, args.only, args.progress)
+    res = run_matrix(args.device, args.only, args.progress, args.compute_dtype)
     text = []
     for name, lines, _ in res:
         text += [summary_line(name, lines)] if args.summary else ["## " + name] + lines
