@@ -6,10 +6,12 @@
 //   adam        : 24 B/element (read g, m, v; write m, v, delta) (+4 with zero_grad)
 #include "hdp_common.h"
 #include "hdp_sr.h"
+#include "hdp_stream_plan.h"
 
 namespace hdp {
 
 constexpr int kEwThreads = 256;
+static_assert(kEwThreads == kStreamThreads, "the stream plan counts chunks in workgroups of kEwThreads");
 typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
 
 static int ew_grid(int64_t vec_items, int per_thread) {
@@ -151,227 +153,6 @@ __global__ void merge_bf16dw_scalar_kernel(uint16_t* W, const uint16_t* dW, int6
     W[i] = f32_to_bf16(bf16_to_f32(W[i]) + bf16_to_f32(dW[i]));
 }
 
-// ---------------------------------------------------------------------------------------
-// Rank-ordered bf16 fold (hp:389-392 for a bf16 model): out = 0; out = bf16(out + parts[i]) for
-// i = 0 .. nparts - 1, one 4-element vector per lane and grid-stride; the parts are read once.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kEwThreads) void fold_bf16_kernel(const float* __restrict__ parts, int nparts,
-                                                                int64_t stride, uint16_t* __restrict__ out,
-                                                                int64_t n, int vec) {
-  const int64_t nv = vec ? n / 4 : 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
-    float run[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int p = 0; p < nparts; ++p) {
-      const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const HDP_GLOBAL f32x4*>(gptr(parts + p * stride)) + i);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) run[q] = bf16_to_f32(f32_to_bf16(run[q] + v[q]));
-    }
-    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    const u32x2 o{(uint32_t)f32_to_bf16(run[0]) | ((uint32_t)f32_to_bf16(run[1]) << 16),
-                  (uint32_t)f32_to_bf16(run[2]) | ((uint32_t)f32_to_bf16(run[3]) << 16)};
-    *reinterpret_cast<HDP_GLOBAL u32x2*>(gptr(out + 4 * i)) = o;
-  }
-  for (int64_t e = 4 * nv + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
-    float run = 0.f;
-    for (int p = 0; p < nparts; ++p) run = bf16_to_f32(f32_to_bf16(run + parts[p * stride + e]));
-    out[e] = f32_to_bf16(run);
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Grouped contiguous copy (hdp_copy_group): the shard exchange's pack (own W rows -> send buffer) and
-// scatter (the other ranks' rows -> W) as one launch over {dst, src, bytes} ranges.  merge_chunk_kernel's
-// form without the arithmetic: one flat chunk space over the items, a workgroup owns kCopyU x 256
-// consecutive 16-byte vectors at a time, every load of the chunk issued before its first store,
-// non-temporal both ways (each byte touched once).  An item whose dst and src sit alike within 16 bytes
-// is split into head bytes up to dst's next 16-byte boundary, whole vectors, and tail bytes; the lanes of
-// the item's first chunk copy the (at most 15 + 15) head and tail bytes one by one.  An item whose
-// pointers sit differently is copied byte by byte over the same chunk walk.
-// ---------------------------------------------------------------------------------------
-constexpr int kCopyU = 8;             // vectors per lane per chunk
-constexpr int kCopyGroupMax = 170;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-struct CopyGroupArgs {
-  int n;
-  hdp_copy_item it[kCopyGroupMax];
-};
-static_assert(sizeof(CopyGroupArgs) <= 4096, "copy group kernel arguments must stay within 4 KB");
-constexpr int64_t kCopyChunk = (int64_t)kEwThreads * kCopyU;  // vectors (aligned item) per chunk
-
-// the split of one item (bytes > 0): head bytes, whole vectors and the chunks it owns; vec = false for an
-// item copied byte by byte (a chunk is then kCopyChunk * 16 bytes)
-struct CopySplit {
-  bool vec;
-  int64_t head, nv, nch;
-};
-__host__ __device__ inline CopySplit copy_split(const void* dst, const void* src, int64_t bytes) {
-  CopySplit s;
-  const uintptr_t d = reinterpret_cast<uintptr_t>(dst), q = reinterpret_cast<uintptr_t>(src);
-  s.vec = ((d ^ q) & 15u) == 0;
-  if (s.vec) {
-    const int64_t h = (int64_t)((16u - (d & 15u)) & 15u);
-    s.head = h < bytes ? h : bytes;
-    s.nv = (bytes - s.head) >> 4;
-    s.nch = s.nv ? (s.nv + kCopyChunk - 1) / kCopyChunk : 1;  // (head / tail only: still one chunk)
-  } else {
-    s.head = 0;
-    s.nv = 0;
-    s.nch = (bytes + kCopyChunk * 16 - 1) / (kCopyChunk * 16);
-  }
-  return s;
-}
-
-__global__ __launch_bounds__(kEwThreads) void copy_chunk_kernel(CopyGroupArgs ga) {
-  int it = 0;
-  CopySplit sp = copy_split(ga.it[0].dst, ga.it[0].src, ga.it[0].bytes);
-  int64_t base = 0;                                     // item it owns chunks [base, base + sp.nch)
-  for (int64_t c = blockIdx.x;; c += gridDim.x) {      // c, it, base, sp: workgroup-uniform
-    while (c >= base + sp.nch) {
-      base += sp.nch;
-      if (++it == ga.n) return;
-      sp = copy_split(ga.it[it].dst, ga.it[it].src, ga.it[it].bytes);
-    }
-    const int64_t bytes = ga.it[it].bytes;
-    HDP_GLOBAL uint8_t* D1 = gptr(reinterpret_cast<uint8_t*>(ga.it[it].dst));
-    const HDP_GLOBAL uint8_t* S1 = gptr(reinterpret_cast<const uint8_t*>(ga.it[it].src));
-    if (sp.vec) {
-      HDP_GLOBAL u32x4* D4 = reinterpret_cast<HDP_GLOBAL u32x4*>(D1 + sp.head);
-      const HDP_GLOBAL u32x4* S4 = reinterpret_cast<const HDP_GLOBAL u32x4*>(S1 + sp.head);
-      const int64_t v0 = (c - base) * kCopyChunk + threadIdx.x;
-      u32x4 x[kCopyU];
-#pragma unroll
-      for (int u = 0; u < kCopyU; ++u) {
-        const int64_t i = v0 + u * kEwThreads;
-        if (i < sp.nv) x[u] = __builtin_nontemporal_load(S4 + i);
-      }
-#pragma unroll
-      for (int u = 0; u < kCopyU; ++u) {
-        const int64_t i = v0 + u * kEwThreads;
-        if (i < sp.nv) __builtin_nontemporal_store(x[u], D4 + i);
-      }
-      if (c == base) {  // the item's first chunk: head bytes on lanes 0-15, tail bytes on lanes 16-31
-        const int64_t t0 = sp.head + 16 * sp.nv;
-        const int l = threadIdx.x;
-        if (l < sp.head) D1[l] = S1[l];
-        else if (l >= 16 && l < 32 && t0 + (l - 16) < bytes) D1[t0 + (l - 16)] = S1[t0 + (l - 16)];
-      }
-    } else {
-      const int64_t b0 = (c - base) * kCopyChunk * 16 + threadIdx.x;
-      uint8_t x[2 * kCopyU];
-      for (int64_t o = 0; o < kCopyChunk * 16; o += (int64_t)kEwThreads * 2 * kCopyU) {
-#pragma unroll
-        for (int u = 0; u < 2 * kCopyU; ++u) {
-          const int64_t i = b0 + o + u * kEwThreads;
-          if (i < bytes) x[u] = S1[i];
-        }
-#pragma unroll
-        for (int u = 0; u < 2 * kCopyU; ++u) {
-          const int64_t i = b0 + o + u * kEwThreads;
-          if (i < bytes) D1[i] = x[u];
-        }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Grouped float32 -> bf16 cast (hdp_shadow_group): the bf16 compute copy of float32 master weights
-// (compute_dtype=), refreshed after a bucket's merge in one launch instead of one copy_ per module.
-// dst[i] = f32_to_bf16(src[i]).  copy_chunk_kernel's form with the conversion between the loads and the
-// stores, 6 B per element: one flat chunk space over the items, a workgroup owns kShadowU x 256 consecutive
-// 8-element vectors at a time (two 16-byte float32 loads and one 16-byte store each), every load of the
-// chunk issued before its first store, non-temporal both ways (each byte touched once).  An item with dst
-// and src both 16-byte aligned runs as vectors, its n % 8 tail elements one per lane on its first chunk (an
-// item shorter than one vector still owns that chunk); any other item runs element by element over the
-// same chunk walk, with the same bits.
-// ---------------------------------------------------------------------------------------
-constexpr int kShadowU = 8;           // vectors per lane per chunk
-constexpr int kShadowGroupMax = 170;
-struct ShadowGroupArgs {
-  int n;
-  hdp_shadow_item it[kShadowGroupMax];
-};
-static_assert(sizeof(ShadowGroupArgs) <= 4096, "shadow group kernel arguments must stay within 4 KB");
-constexpr int64_t kShadowChunk = (int64_t)kEwThreads * kShadowU;  // vectors per chunk (8 elements each)
-
-// the split of one item (n > 0): whether it runs as vectors, how many, and the chunks it owns
-struct ShadowSplit {
-  bool vec;
-  int64_t nv, nch;
-};
-__host__ __device__ inline ShadowSplit shadow_split(const void* dst, const void* src, int64_t n) {
-  ShadowSplit s;
-  s.vec = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15u) == 0;
-  if (s.vec) {
-    s.nv = n >> 3;
-    s.nch = s.nv ? (s.nv + kShadowChunk - 1) / kShadowChunk : 1;  // (tail only: still one chunk)
-  } else {
-    s.nv = 0;
-    s.nch = (n + kShadowChunk * 8 - 1) / (kShadowChunk * 8);
-  }
-  return s;
-}
-
-__global__ __launch_bounds__(kEwThreads) void shadow_chunk_kernel(ShadowGroupArgs ga) {
-  int it = 0;
-  ShadowSplit sp = shadow_split(ga.it[0].dst, ga.it[0].src, ga.it[0].n);
-  int64_t base = 0;                                     // item it owns chunks [base, base + sp.nch)
-  for (int64_t c = blockIdx.x;; c += gridDim.x) {      // c, it, base, sp: workgroup-uniform
-    while (c >= base + sp.nch) {
-      base += sp.nch;
-      if (++it == ga.n) return;
-      sp = shadow_split(ga.it[it].dst, ga.it[it].src, ga.it[it].n);
-    }
-    const int64_t n = ga.it[it].n;
-    HDP_GLOBAL uint16_t* D1 = gptr(reinterpret_cast<uint16_t*>(ga.it[it].dst));
-    const HDP_GLOBAL float* S1 = gptr(ga.it[it].src);
-    if (sp.vec) {
-      HDP_GLOBAL u32x4* D8 = reinterpret_cast<HDP_GLOBAL u32x4*>(D1);
-      const HDP_GLOBAL f32x4* S4 = reinterpret_cast<const HDP_GLOBAL f32x4*>(S1);
-      const int64_t v0 = (c - base) * kShadowChunk + threadIdx.x;
-      f32x4 x0[kShadowU], x1[kShadowU];
-#pragma unroll
-      for (int u = 0; u < kShadowU; ++u) {
-        const int64_t i = v0 + u * kEwThreads;
-        if (i < sp.nv) {
-          x0[u] = __builtin_nontemporal_load(S4 + 2 * i);
-          x1[u] = __builtin_nontemporal_load(S4 + 2 * i + 1);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kShadowU; ++u) {
-        const int64_t i = v0 + u * kEwThreads;
-        if (i < sp.nv) {
-          const u32x4 o{(uint32_t)f32_to_bf16(x0[u][0]) | ((uint32_t)f32_to_bf16(x0[u][1]) << 16),
-                        (uint32_t)f32_to_bf16(x0[u][2]) | ((uint32_t)f32_to_bf16(x0[u][3]) << 16),
-                        (uint32_t)f32_to_bf16(x1[u][0]) | ((uint32_t)f32_to_bf16(x1[u][1]) << 16),
-                        (uint32_t)f32_to_bf16(x1[u][2]) | ((uint32_t)f32_to_bf16(x1[u][3]) << 16)};
-          __builtin_nontemporal_store(o, D8 + i);
-        }
-      }
-      if (c == base) {  // the item's first chunk: the n % 8 tail elements, one per lane
-        const int64_t j = 8 * sp.nv + threadIdx.x;
-        if (threadIdx.x < 8 && j < n) D1[j] = f32_to_bf16(S1[j]);
-      }
-    } else {
-      const int64_t e0 = (c - base) * kShadowChunk * 8 + threadIdx.x;
-      float x[2 * kShadowU];
-      for (int64_t o = 0; o < kShadowChunk * 8; o += (int64_t)kEwThreads * 2 * kShadowU) {
-#pragma unroll
-        for (int u = 0; u < 2 * kShadowU; ++u) {
-          const int64_t i = e0 + o + u * kEwThreads;
-          if (i < n) x[u] = S1[i];
-        }
-#pragma unroll
-        for (int u = 0; u < 2 * kShadowU; ++u) {
-          const int64_t i = e0 + o + u * kEwThreads;
-          if (i < n) D1[i] = f32_to_bf16(x[u]);
-        }
-      }
-    }
-  }
-}
-
 static int merge_chunk_launch(const MergeGroupArgs& ga, bool bf16, double bytes, hipStream_t st) {
   // the chunk the kernel walks (merge_chunk_kernel<BF>'s U): the grid never exceeds the chunk count
   const int64_t CH = (int64_t)kEwThreads * (bf16 ? 2 * kMergeU : kMergeU);
@@ -400,50 +181,55 @@ __global__ void merge_scalar_kernel(void* W, int dt, const float* dW, int64_t be
 }
 
 // ---------------------------------------------------------------------------------------
-// Stochastic-rounding merge (hdp_merge_group_sr; contract in hdp_sr.h): bf16 W = sr(float32(W) + dW) from
-// the float32 sum, 8 B per element like merge_chunk_kernel<true> and in its form -- one flat chunk space
-// over the items, a workgroup owns 2 kMergeU x 256 consecutive 8-element vectors at a time, every load of
-// the chunk issued before its first store, non-temporal both ways.  One Philox block per vector (element
-// index e = elem0 + 8 i, a multiple of 8): ~40 32-bit multiplies and ~60 other VALU operations per 64 bytes
-// of traffic.  The n % 8 tail elements of an item are merged one per lane by the item's first chunk (an
-// item shorter than one vector still owns that chunk).  Items that cannot take the vector path (W or dW off
-// 16 bytes, elem0 % 8 != 0) run merge_sr_scalar_kernel: the same function per element, the same e.
+// The grouped stream kernels behind one walk: the stochastic-rounding merge of hdp_sr.h, the grouped copy of
+// the shard exchange's pack and scatter, and the float32 -> bf16 cast of the compute copies (compute_dtype=).
+// (The round-to-nearest merges above keep their own kernels: through this walk they measured 2-6 % slower,
+// DESIGN section 5.)  stream_group_kernel<Op>:
+//   * one flat chunk space over a launch's items; a workgroup walks chunks blockIdx.x, + grid, ... and owns
+//     Op::kU x 256 consecutive 16-byte vectors (of dst) at a time, every load of the chunk issued before its
+//     first store, non-temporal both ways (each byte is touched once).  tools/merge_bw.hip on a 1 GiB
+//     float32 slab: this form 5.76 TB/s (0.72 of 8) against 4.61 for a grid-stride loop with two vectors per
+//     lane (profiles/r03_merge_bw_v2.txt);
+//   * an item that can take vectors (hdp_stream_plan.h: dst and src 16-byte aligned; the copy: sitting alike
+//     within 16 bytes, behind head bytes up to dst's boundary; SR: elem0 % 8 == 0 as well, one Philox block
+//     per vector) has its head and tail units moved one per lane by its first chunk, so an item shorter than
+//     one vector still owns that chunk;
+//   * any other item runs unit by unit over the same chunk walk, in the same launch, with the same bits.
+// An Op is its plan (item type, cap, kU, kVec, split) plus the arithmetic: vec_chunk for a lane's kU vectors
+// of one chunk, load1 / store1 for one unit (edge lanes and unit-by-unit items).  SR costs ~40 32-bit multiplies and ~60 other VALU operations per 64 bytes of traffic.
 // ---------------------------------------------------------------------------------------
-struct MergeSrArgs {
-  int n;
-  uint32_t seed_lo, seed_hi;
-  void* W[kMergeGroupMax];
-  const float* dW[kMergeGroupMax];
-  int64_t cnt[kMergeGroupMax];      // elements (vectors: cnt / 8, tail: cnt % 8)
-  uint64_t elem0[kMergeGroupMax];   // element index of the item's first element (% 8 == 0)
-  uint64_t offset[kMergeGroupMax];  // the item's Philox offset
-};
-static_assert(sizeof(MergeSrArgs) <= 4096, "merge sr kernel arguments must stay within 4 KB");
-constexpr int64_t kMergeSrChunk = (int64_t)kEwThreads * 2 * kMergeU;  // vectors per chunk
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+template <class T>
+__device__ __forceinline__ HDP_GLOBAL T* gptr_as(void* p) { return gptr(reinterpret_cast<T*>(p)); }
+template <class T>
+__device__ __forceinline__ const HDP_GLOBAL T* gptr_as(const void* p) { return gptr(reinterpret_cast<const T*>(p)); }
 
-// chunks an item of cnt > 0 elements owns (at least one: the tail rides on the first)
-__host__ __device__ inline int64_t merge_sr_chunks(int64_t cnt) {
-  const int64_t nv = cnt >> 3;
-  return nv ? (nv + kMergeSrChunk - 1) / kMergeSrChunk : 1;
-}
+// (inline, not __forceinline__: inlined ahead of the optimiser, hipcc makes one wide vector of a chunk's
+// register arrays and waits for every load on its own -- 256 VGPRs for the copy against 70)
+#define HDP_OP_FN static __device__ inline
 
-__global__ __launch_bounds__(kEwThreads) void merge_sr_chunk_kernel(MergeSrArgs ga) {
-  constexpr int U = 2 * kMergeU;
-  constexpr int64_t CH = kMergeSrChunk;
-  int it = 0;
-  int64_t base = 0, nch = merge_sr_chunks(ga.cnt[0]);    // item it owns chunks [base, base + nch)
-  for (int64_t c = blockIdx.x;; c += gridDim.x) {        // c, it, base: workgroup-uniform
-    while (c >= base + nch) {
-      base += nch;
-      if (++it == ga.n) return;
-      nch = merge_sr_chunks(ga.cnt[it]);
-    }
-    const int64_t cnt = ga.cnt[it], nv = cnt >> 3;
-    const int64_t v0 = (c - base) * CH + threadIdx.x;
-    const uint64_t off = ga.offset[it], e0 = ga.elem0[it];
-    const SrKey key{ga.seed_lo, ga.seed_hi, static_cast<uint32_t>(off), static_cast<uint32_t>(off >> 32)};
-    const HDP_GLOBAL f32x4* D4 = reinterpret_cast<const HDP_GLOBAL f32x4*>(gptr(ga.dW[it]));
-    HDP_GLOBAL u16x8* W8 = reinterpret_cast<HDP_GLOBAL u16x8*>(gptr(reinterpret_cast<uint16_t*>(ga.W[it])));
+// bf16 W = sr(float32(W) + dW) (contract in hdp_sr.h), 8 B per element: element j of an item has e = elem0 + j,
+// a vector one Philox block
+struct MergeSrOp : MergeSrPlan {
+  struct Elem {
+    uint16_t w;
+    float d;
+  };
+  HDP_OP_FN SrKey key_of(const Item& it, const SrSeed& seed) {
+    return SrKey{seed.lo, seed.hi, static_cast<uint32_t>(it.offset), static_cast<uint32_t>(it.offset >> 32)};
+  }
+  HDP_OP_FN Elem load1(const Item& it, int64_t j) { return Elem{gptr_as<uint16_t>(it.W)[j], gptr(it.dW)[j]}; }
+  HDP_OP_FN void store1(const Item& it, const SrSeed& seed, int64_t j, const Elem& e) {
+    gptr_as<uint16_t>(it.W)[j] =
+        sr_merge1(e.w, e.d, sr_r16(static_cast<uint64_t>(it.elem0) + static_cast<uint64_t>(j), key_of(it, seed)));
+  }
+  HDP_OP_FN void vec_chunk(const Item& it, const SrSeed& seed, const StreamSplit& sp, int64_t v0) {
+    constexpr int U = kU;
+    const int64_t nv = sp.nv;
+    const uint64_t e0 = static_cast<uint64_t>(it.elem0);
+    const SrKey key = key_of(it, seed);
+    const HDP_GLOBAL f32x4* D4 = gptr_as<f32x4>(it.dW);
+    HDP_GLOBAL u16x8* W8 = gptr_as<u16x8>(it.W);
     u16x8 w[U];
     f32x4 d0[U], d1[U];
 #pragma unroll
@@ -472,21 +258,152 @@ __global__ __launch_bounds__(kEwThreads) void merge_sr_chunk_kernel(MergeSrArgs 
         __builtin_nontemporal_store(__builtin_bit_cast(u16x8, o), W8 + i);
       }
     }
-    if (c == base) {  // the item's first chunk: the cnt % 8 tail elements, one per lane
-      const int64_t j = 8 * nv + threadIdx.x;
-      if (threadIdx.x < 8 && j < cnt) {
-        HDP_GLOBAL uint16_t* W1 = gptr(reinterpret_cast<uint16_t*>(ga.W[it]));
-        const float d = *gptr(ga.dW[it] + j);
-        W1[j] = sr_merge1(W1[j], d, sr_r16(e0 + static_cast<uint64_t>(j), key));
+  }
+};
+
+// dst <- src, bytes
+struct CopyOp : CopyPlan {
+  using Elem = uint8_t;
+  HDP_OP_FN Elem load1(const Item& it, int64_t j) { return gptr_as<uint8_t>(it.src)[j]; }
+  HDP_OP_FN void store1(const Item& it, const NoKey&, int64_t j, Elem x) { gptr_as<uint8_t>(it.dst)[j] = x; }
+  HDP_OP_FN void vec_chunk(const Item& it, const NoKey&, const StreamSplit& sp, int64_t v0) {
+    HDP_GLOBAL u32x4* D4 = reinterpret_cast<HDP_GLOBAL u32x4*>(gptr_as<uint8_t>(it.dst) + sp.head);
+    const HDP_GLOBAL u32x4* S4 = reinterpret_cast<const HDP_GLOBAL u32x4*>(gptr_as<uint8_t>(it.src) + sp.head);
+    u32x4 x[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int64_t i = v0 + u * kEwThreads;
+      if (i < sp.nv) x[u] = __builtin_nontemporal_load(S4 + i);
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int64_t i = v0 + u * kEwThreads;
+      if (i < sp.nv) __builtin_nontemporal_store(x[u], D4 + i);
+    }
+  }
+};
+
+// bf16 dst <- f32_to_bf16(float32 src), 6 B per element: two 16-byte loads and one 16-byte store per vector
+struct ShadowOp : ShadowPlan {
+  using Elem = float;
+  HDP_OP_FN Elem load1(const Item& it, int64_t j) { return gptr(it.src)[j]; }
+  HDP_OP_FN void store1(const Item& it, const NoKey&, int64_t j, Elem x) { gptr_as<uint16_t>(it.dst)[j] = f32_to_bf16(x); }
+  HDP_OP_FN void vec_chunk(const Item& it, const NoKey&, const StreamSplit& sp, int64_t v0) {
+    HDP_GLOBAL u32x4* D8 = gptr_as<u32x4>(it.dst);
+    const HDP_GLOBAL f32x4* S4 = gptr_as<f32x4>(it.src);
+    f32x4 x0[kU], x1[kU];
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int64_t i = v0 + u * kEwThreads;
+      if (i < sp.nv) {
+        x0[u] = __builtin_nontemporal_load(S4 + 2 * i);
+        x1[u] = __builtin_nontemporal_load(S4 + 2 * i + 1);
       }
+    }
+#pragma unroll
+    for (int u = 0; u < kU; ++u) {
+      const int64_t i = v0 + u * kEwThreads;
+      if (i < sp.nv) {
+        const u32x4 o{(uint32_t)f32_to_bf16(x0[u][0]) | ((uint32_t)f32_to_bf16(x0[u][1]) << 16),
+                      (uint32_t)f32_to_bf16(x0[u][2]) | ((uint32_t)f32_to_bf16(x0[u][3]) << 16),
+                      (uint32_t)f32_to_bf16(x1[u][0]) | ((uint32_t)f32_to_bf16(x1[u][1]) << 16),
+                      (uint32_t)f32_to_bf16(x1[u][2]) | ((uint32_t)f32_to_bf16(x1[u][3]) << 16)};
+        __builtin_nontemporal_store(o, D8 + i);
+      }
+    }
+  }
+};
+#undef HDP_OP_FN
+
+template <class Op>
+__global__ __launch_bounds__(kEwThreads) void stream_group_kernel(StreamArgs<Op> ga) {
+  constexpr int64_t CH = (int64_t)kEwThreads * Op::kU;  // vectors per chunk
+  int it = 0;
+  StreamSplit sp = Op::split(ga.it[0]);
+  int64_t base = 0;                                     // item it owns chunks [base, base + sp.nch)
+  for (int64_t c = blockIdx.x;; c += gridDim.x) {      // c, it, base, sp: workgroup-uniform
+    while (c >= base + sp.nch) {
+      base += sp.nch;
+      if (++it == ga.n) return;
+      sp = Op::split(ga.it[it]);
+    }
+    const typename Op::Item& item = ga.it[it];
+    const int64_t n = Op::count(item);
+    if (!sp.vec) {  // unit by unit over the chunk
+      // (x is zeroed for every step: left unwritten where i >= n, hipcc carries its registers round the chunk
+      // loop and costs registers on the vector path)
+      constexpr int N = Op::kElemU;
+      static_assert(Op::kU * Op::kVec % N == 0, "whole steps per chunk");
+      const int64_t e0 = (c - base) * CH * Op::kVec + threadIdx.x;
+#pragma nounroll
+      for (int64_t o = 0; o < CH * Op::kVec; o += (int64_t)kEwThreads * N) {
+        typename Op::Elem x[N] = {};
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+          const int64_t i = e0 + o + u * kEwThreads;
+          if (i < n) x[u] = Op::load1(item, i);
+        }
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+          const int64_t i = e0 + o + u * kEwThreads;
+          if (i < n) Op::store1(item, ga.key, i, x[u]);
+        }
+      }
+      continue;
+    }
+    Op::vec_chunk(item, ga.key, sp, (c - base) * CH + threadIdx.x);
+    if (c == base) {  // the item's first chunk: head and tail units, one per lane
+      const int64_t j = stream_edge_unit<Op>(sp, threadIdx.x, n);
+      if (j >= 0) Op::store1(item, ga.key, j, Op::load1(item, j));
     }
   }
 }
 
-// element-wise form (an item off the vector path's alignment): element j has e = elem0 + j
-__global__ void merge_sr_scalar_kernel(uint16_t* W, const float* dW, int64_t n, uint64_t elem0, SrKey key) {
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x)
-    W[j] = sr_merge1(W[j], dW[j], sr_r16(elem0 + static_cast<uint64_t>(j), key));
+// every item checked before the first launch, then one launch per Op::kCap non-empty items
+template <class Op>
+static int stream_group_run(const char* who, int kid, int n, const typename Op::Item* items, const typename Op::Key& key,
+                            void* stream) {
+  char err[192];
+  if (!stream_check<Op>(who, n, items, err, sizeof(err))) {
+    set_error("%s", err);
+    return HDP_EINVAL;
+  }
+  hipStream_t st = as_stream(stream);
+  return stream_batch<Op>(n, items, key, [&](const StreamArgs<Op>& ga, int64_t chunks, double bytes) -> int {
+    {
+      KTimer kt(kid, st, bytes);
+      hipLaunchKernelGGL(stream_group_kernel<Op>, dim3(stream_grid(chunks)), dim3(kEwThreads), 0, st, ga);
+    }
+    HDP_CHECK_LAUNCH();
+    return HDP_OK;
+  });
+}
+
+// ---------------------------------------------------------------------------------------
+// Rank-ordered bf16 fold (hp:389-392 for a bf16 model): out = 0; out = bf16(out + parts[i]) for
+// i = 0 .. nparts - 1, one 4-element vector per lane and grid-stride; the parts are read once.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kEwThreads) void fold_bf16_kernel(const float* __restrict__ parts, int nparts,
+                                                                int64_t stride, uint16_t* __restrict__ out,
+                                                                int64_t n, int vec) {
+  const int64_t nv = vec ? n / 4 : 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
+    float run[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int p = 0; p < nparts; ++p) {
+      const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const HDP_GLOBAL f32x4*>(gptr(parts + p * stride)) + i);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) run[q] = bf16_to_f32(f32_to_bf16(run[q] + v[q]));
+    }
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 o{(uint32_t)f32_to_bf16(run[0]) | ((uint32_t)f32_to_bf16(run[1]) << 16),
+                  (uint32_t)f32_to_bf16(run[2]) | ((uint32_t)f32_to_bf16(run[3]) << 16)};
+    *reinterpret_cast<HDP_GLOBAL u32x2*>(gptr(out + 4 * i)) = o;
+  }
+  for (int64_t e = 4 * nv + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    float run = 0.f;
+    for (int p = 0; p < nparts; ++p) run = bf16_to_f32(f32_to_bf16(run + parts[p * stride + e]));
+    out[e] = f32_to_bf16(run);
+  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -729,8 +646,18 @@ extern "C" int hdp_merge(void* W, int w_dtype, const float* dW, int64_t n, void*
   return HDP_OK;
 }
 
+// every item of a merge list before the first launch: the merges work on W in place
+static int merge_items_check(const char* who, int n, const hdp_merge_item* items) {
+  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "%s: bad item list", who);
+  for (int i = 0; i < n; ++i) {
+    HDP_CHECK_ARG(items[i].n >= 0, "%s: item %d has n < 0", who, i);
+    HDP_CHECK_ARG(items[i].n == 0 || (items[i].W && items[i].dW), "%s: item %d has a null pointer", who, i);
+  }
+  return HDP_OK;
+}
+
 extern "C" int hdp_merge_group(int n, const hdp_merge_item* items, int w_dtype, void* stream) {
-  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "hdp_merge_group: bad item list");
+  if (const int rc = merge_items_check("hdp_merge_group", n, items)) return rc;
   HDP_CHECK_ARG(w_dtype == HDP_F32 || w_dtype == HDP_BF16, "hdp_merge_group: bad dtype %d", w_dtype);
   hipStream_t st = as_stream(stream);
   const int64_t vec = w_dtype == HDP_F32 ? 4 : 8;
@@ -746,7 +673,6 @@ extern "C" int hdp_merge_group(int n, const hdp_merge_item* items, int w_dtype, 
   };
   for (int i = 0; i < n; ++i) {
     const hdp_merge_item& it = items[i];
-    HDP_CHECK_ARG(it.n >= 0 && (it.n == 0 || (it.W && it.dW)), "hdp_merge_group: bad item %d", i);
     if (it.n == 0) continue;
     if (!aligned16(it.W) || !aligned16(it.dW) || it.n % vec != 0) {  // this item on its own
       const int rc = hdp_merge(it.W, w_dtype, it.dW, it.n, stream);
@@ -765,28 +691,20 @@ extern "C" int hdp_merge_group(int n, const hdp_merge_item* items, int w_dtype, 
   return launch();
 }
 
-extern "C" int hdp_merge_group_sr(int n, const hdp_merge_sr_item* items, uint64_t seed, void* stream) {
-  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "hdp_merge_group_sr: bad item list");
-  for (int i = 0; i < n; ++i) {  // all of it before the first launch
-    const hdp_merge_sr_item& it = items[i];
-    HDP_CHECK_ARG(it.n >= 0 && it.elem0 >= 0, "hdp_merge_group_sr: item %d has n < 0 or elem0 < 0", i);
-    HDP_CHECK_ARG(it.n == 0 || (it.W && it.dW), "hdp_merge_group_sr: item %d has a null pointer", i);
-    HDP_CHECK_ARG(it.n == 0 || ((reinterpret_cast<uintptr_t>(it.W) & 1u) == 0 && (reinterpret_cast<uintptr_t>(it.dW) & 3u) == 0),
-                  "hdp_merge_group_sr: item %d: W must be 2-byte and dW 4-byte aligned", i);
-  }
+extern "C" int hdp_merge_group_bf16dw(int n, const hdp_merge_item* items, void* stream) {
+  if (const int rc = merge_items_check("hdp_merge_group_bf16dw", n, items)) return rc;
   hipStream_t st = as_stream(stream);
-  MergeSrArgs ga;
+  MergeGroupArgs ga;
   ga.n = 0;
-  ga.seed_lo = static_cast<uint32_t>(seed);
-  ga.seed_hi = static_cast<uint32_t>(seed >> 32);
   double bytes = 0;
   int64_t chunks = 0;
+  constexpr int64_t CH = (int64_t)kEwThreads * kMergeU;
   auto launch = [&]() -> int {
     if (ga.n == 0) return HDP_OK;
     const unsigned grid = (unsigned)(chunks < kMergeGrid ? chunks : kMergeGrid);
     {
-      KTimer kt(K_MERGE_SR, st, bytes);
-      hipLaunchKernelGGL(merge_sr_chunk_kernel, dim3(grid), dim3(kEwThreads), 0, st, ga);
+      KTimer kt(K_MERGE, st, bytes);
+      hipLaunchKernelGGL(merge_bf16dw_kernel, dim3(grid), dim3(kEwThreads), 0, st, ga);
     }
     HDP_CHECK_LAUNCH();
     ga.n = 0;
@@ -795,32 +713,43 @@ extern "C" int hdp_merge_group_sr(int n, const hdp_merge_sr_item* items, uint64_
     return HDP_OK;
   };
   for (int i = 0; i < n; ++i) {
-    const hdp_merge_sr_item& it = items[i];
+    const hdp_merge_item& it = items[i];
     if (it.n == 0) continue;
-    if (!aligned16(it.W) || !aligned16(it.dW) || it.elem0 % 8 != 0) {  // this item element-wise
+    if (!aligned16(it.W) || !aligned16(it.dW) || it.n % 8 != 0) {  // this item element-wise
       int blocks = (int)((it.n + 255) / 256);
       if (blocks > 2048) blocks = 2048;
       {
-        KTimer kt(K_MERGE_SR, st, 8.0 * it.n);
-        hipLaunchKernelGGL(merge_sr_scalar_kernel, dim3(blocks), dim3(256), 0, st, reinterpret_cast<uint16_t*>(it.W),
-                           it.dW, it.n, static_cast<uint64_t>(it.elem0), sr_key(seed, it.offset));
+        KTimer kt(K_MERGE, st, 6.0 * it.n);
+        hipLaunchKernelGGL(merge_bf16dw_scalar_kernel, dim3(blocks), dim3(256), 0, st,
+                           reinterpret_cast<uint16_t*>(it.W), reinterpret_cast<const uint16_t*>(it.dW), it.n);
       }
       HDP_CHECK_LAUNCH();
       continue;
     }
     ga.W[ga.n] = it.W;
     ga.dW[ga.n] = it.dW;
-    ga.cnt[ga.n] = it.n;
-    ga.elem0[ga.n] = static_cast<uint64_t>(it.elem0);
-    ga.offset[ga.n] = it.offset;
-    chunks += merge_sr_chunks(it.n);
-    bytes += 8.0 * it.n;
+    ga.nv[ga.n] = it.n / 8;
+    chunks += (ga.nv[ga.n] + CH - 1) / CH;
+    bytes += 6.0 * it.n;
     if (++ga.n == kMergeGroupMax) {
       const int rc = launch();
       if (rc) return rc;
     }
   }
   return launch();
+}
+
+extern "C" int hdp_merge_group_sr(int n, const hdp_merge_sr_item* items, uint64_t seed, void* stream) {
+  const SrSeed key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)};
+  return stream_group_run<MergeSrOp>("hdp_merge_group_sr", K_MERGE_SR, n, items, key, stream);
+}
+
+extern "C" int hdp_copy_group(int n, const hdp_copy_item* items, void* stream) {
+  return stream_group_run<CopyOp>("hdp_copy_group", K_COPY, n, items, NoKey{}, stream);
+}
+
+extern "C" int hdp_shadow_group(int n, const hdp_shadow_item* items, void* stream) {
+  return stream_group_run<ShadowOp>("hdp_shadow_group", K_SHADOW, n, items, NoKey{}, stream);
 }
 
 static int adam_factors_impl(const char* who, float* grad, float* m, float* v, float* delta, int64_t n,
@@ -959,132 +888,6 @@ extern "C" int hdp_clip_finish(const double* sums, int nsums, float max_norm, hd
   }
   HDP_CHECK_LAUNCH();
   return HDP_OK;
-}
-
-extern "C" int hdp_merge_group_bf16dw(int n, const hdp_merge_item* items, void* stream) {
-  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "hdp_merge_group_bf16dw: bad item list");
-  hipStream_t st = as_stream(stream);
-  MergeGroupArgs ga;
-  ga.n = 0;
-  double bytes = 0;
-  int64_t chunks = 0;
-  constexpr int64_t CH = (int64_t)kEwThreads * kMergeU;
-  auto launch = [&]() -> int {
-    if (ga.n == 0) return HDP_OK;
-    const unsigned grid = (unsigned)(chunks < kMergeGrid ? chunks : kMergeGrid);
-    {
-      KTimer kt(K_MERGE, st, bytes);
-      hipLaunchKernelGGL(merge_bf16dw_kernel, dim3(grid), dim3(kEwThreads), 0, st, ga);
-    }
-    HDP_CHECK_LAUNCH();
-    ga.n = 0;
-    bytes = 0;
-    chunks = 0;
-    return HDP_OK;
-  };
-  for (int i = 0; i < n; ++i) {
-    const hdp_merge_item& it = items[i];
-    HDP_CHECK_ARG(it.n >= 0 && (it.n == 0 || (it.W && it.dW)), "hdp_merge_group_bf16dw: bad item %d", i);
-    if (it.n == 0) continue;
-    if (!aligned16(it.W) || !aligned16(it.dW) || it.n % 8 != 0) {  // this item element-wise
-      int blocks = (int)((it.n + 255) / 256);
-      if (blocks > 2048) blocks = 2048;
-      {
-        KTimer kt(K_MERGE, st, 6.0 * it.n);
-        hipLaunchKernelGGL(merge_bf16dw_scalar_kernel, dim3(blocks), dim3(256), 0, st,
-                           reinterpret_cast<uint16_t*>(it.W), reinterpret_cast<const uint16_t*>(it.dW), it.n);
-      }
-      HDP_CHECK_LAUNCH();
-      continue;
-    }
-    ga.W[ga.n] = it.W;
-    ga.dW[ga.n] = it.dW;
-    ga.nv[ga.n] = it.n / 8;
-    chunks += (ga.nv[ga.n] + CH - 1) / CH;
-    bytes += 6.0 * it.n;
-    if (++ga.n == kMergeGroupMax) {
-      const int rc = launch();
-      if (rc) return rc;
-    }
-  }
-  return launch();
-}
-
-extern "C" int hdp_copy_group(int n, const hdp_copy_item* items, void* stream) {
-  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "hdp_copy_group: bad item list");
-  for (int i = 0; i < n; ++i) {  // all of it before the first launch
-    HDP_CHECK_ARG(items[i].bytes >= 0, "hdp_copy_group: item %d has bytes < 0", i);
-    HDP_CHECK_ARG(items[i].bytes == 0 || (items[i].dst && items[i].src), "hdp_copy_group: item %d has a null pointer", i);
-  }
-  hipStream_t st = as_stream(stream);
-  CopyGroupArgs ga;
-  ga.n = 0;
-  double bytes = 0;
-  int64_t chunks = 0;
-  auto launch = [&]() -> int {
-    if (ga.n == 0) return HDP_OK;
-    const unsigned grid = (unsigned)(chunks < kMergeGrid ? chunks : kMergeGrid);
-    {
-      KTimer kt(K_COPY, st, 2.0 * bytes);
-      hipLaunchKernelGGL(copy_chunk_kernel, dim3(grid), dim3(kEwThreads), 0, st, ga);
-    }
-    HDP_CHECK_LAUNCH();
-    ga.n = 0;
-    bytes = 0;
-    chunks = 0;
-    return HDP_OK;
-  };
-  for (int i = 0; i < n; ++i) {
-    if (items[i].bytes == 0) continue;
-    ga.it[ga.n] = items[i];
-    chunks += copy_split(items[i].dst, items[i].src, items[i].bytes).nch;
-    bytes += (double)items[i].bytes;
-    if (++ga.n == kCopyGroupMax) {
-      const int rc = launch();
-      if (rc) return rc;
-    }
-  }
-  return launch();
-}
-
-extern "C" int hdp_shadow_group(int n, const hdp_shadow_item* items, void* stream) {
-  HDP_CHECK_ARG(n >= 0 && (n == 0 || items), "hdp_shadow_group: bad item list");
-  for (int i = 0; i < n; ++i) {  // all of it before the first launch
-    HDP_CHECK_ARG(items[i].n >= 0, "hdp_shadow_group: item %d has n < 0", i);
-    HDP_CHECK_ARG(items[i].n == 0 || (items[i].dst && items[i].src), "hdp_shadow_group: item %d has a null pointer", i);
-    HDP_CHECK_ARG(items[i].n == 0 || ((reinterpret_cast<uintptr_t>(items[i].dst) & 1u) == 0 &&
-                                      (reinterpret_cast<uintptr_t>(items[i].src) & 3u) == 0),
-                  "hdp_shadow_group: item %d: dst must be 2-byte and src 4-byte aligned", i);
-  }
-  hipStream_t st = as_stream(stream);
-  ShadowGroupArgs ga;
-  ga.n = 0;
-  double bytes = 0;
-  int64_t chunks = 0;
-  auto launch = [&]() -> int {
-    if (ga.n == 0) return HDP_OK;
-    const unsigned grid = (unsigned)(chunks < kMergeGrid ? chunks : kMergeGrid);
-    {
-      KTimer kt(K_SHADOW, st, bytes);
-      hipLaunchKernelGGL(shadow_chunk_kernel, dim3(grid), dim3(kEwThreads), 0, st, ga);
-    }
-    HDP_CHECK_LAUNCH();
-    ga.n = 0;
-    bytes = 0;
-    chunks = 0;
-    return HDP_OK;
-  };
-  for (int i = 0; i < n; ++i) {
-    if (items[i].n == 0) continue;
-    ga.it[ga.n] = items[i];
-    chunks += shadow_split(items[i].dst, items[i].src, items[i].n).nch;
-    bytes += 6.0 * (double)items[i].n;
-    if (++ga.n == kShadowGroupMax) {
-      const int rc = launch();
-      if (rc) return rc;
-    }
-  }
-  return launch();
 }
 
 extern "C" int hdp_fold_bf16(const float* parts, int nparts, int64_t stride, void* out, int64_t n, void* stream) {

@@ -52,6 +52,20 @@ def _clip_ptr(state: torch.Tensor) -> int:
     return state.data_ptr()
 
 
+def _stream_pair(what: str, a: str, b: str, dst, src, dst_bf16=False, src_f32=True, in_bytes=False):
+    """One (dst, src) pair of a grouped stream op (merge_group, merge_group_sr, copy_group, shadow_group): of the
+    dtypes the op takes, contiguous and of equal size (the caller has checked the device).  Returns (dst pointer, src pointer, count),
+    the count in elements, or in bytes for the copy.  ``a`` / ``b`` are the op's names for dst and src."""
+    if src_f32:
+        _f32(src)
+    if dst_bf16 and dst.dtype != torch.bfloat16:
+        raise TypeError(f"{what}: {a} must be bfloat16, got {dst.dtype}")
+    per = (dst.element_size(), src.element_size()) if in_bytes else (1, 1)
+    if dst.numel() * per[0] != src.numel() * per[1] or not dst.is_contiguous() or not src.is_contiguous():
+        raise ValueError(f"{what}: {a} and {b} must be contiguous with equal {'byte ' if in_bytes else ''}sizes")
+    return dst.data_ptr(), src.data_ptr(), dst.numel() * per[0]
+
+
 class HipOps:
     """The MI355X kernel set (libhdpissa.so)."""
 
@@ -362,22 +376,17 @@ class HipOps:
             _need_gpu(W, dW)
             if dW.dtype == torch.bfloat16 and W.dtype != torch.bfloat16:
                 raise TypeError("merge_group: a bfloat16 dW needs a bfloat16 W")
-            if dW.dtype != torch.bfloat16:
-                _f32(dW)
-            if W.numel() != dW.numel() or not W.is_contiguous() or not dW.is_contiguous():
-                raise ValueError("merge_group: W and dW must be contiguous with equal sizes")
+            item = _stream_pair("merge_group", "W", "dW", W, dW, src_f32=dW.dtype != torch.bfloat16)
             key = (W.dtype, dW.dtype)
             if not runs or runs[-1][0] != key:
-                runs.append((key, []))
-            runs[-1][1].append((W, dW))
-        for (wdt, ddt), run in runs:
-            arr = (MergeItem * len(run))()
-            for i, (W, dW) in enumerate(run):
-                arr[i].W, arr[i].dW, arr[i].n = W.data_ptr(), dW.data_ptr(), W.numel()
+                runs.append((key, W, []))
+            runs[-1][2].append(item)
+        for (_, ddt), W0, run in runs:
+            arr = (MergeItem * len(run))(*run)
             if ddt == torch.bfloat16:
                 check(lib().hdp_merge_group_bf16dw(len(run), arr, _stream()), "hdp_merge_group_bf16dw")
             else:
-                check(lib().hdp_merge_group(len(run), arr, _dt(run[0][0]), _stream()), "hdp_merge_group")
+                check(lib().hdp_merge_group(len(run), arr, _dt(W0), _stream()), "hdp_merge_group")
 
     def merge_group_sr(self, triples, seed: int) -> None:
         """Stochastic-rounding merge over many ``(W, dW, elem0, offset)`` items (one exchange bucket):
@@ -387,19 +396,15 @@ class HipOps:
         from ._lib import MergeSrItem
         if not triples:
             return
-        arr = (MergeSrItem * len(triples))()
-        for i, (W, dW, elem0, offset) in enumerate(triples):
+        rows = []
+        for W, dW, elem0, offset in triples:
             _need_gpu(W, dW)
-            _f32(dW)
-            if W.dtype != torch.bfloat16:
-                raise TypeError(f"merge_group_sr: W must be bfloat16, got {W.dtype}")
-            if W.numel() != dW.numel() or not W.is_contiguous() or not dW.is_contiguous():
-                raise ValueError("merge_group_sr: W and dW must be contiguous with equal sizes")
+            item = _stream_pair("merge_group_sr", "W", "dW", W, dW, dst_bf16=True)
             if int(elem0) < 0:
                 raise ValueError("merge_group_sr: elem0 must be >= 0")
-            arr[i].W, arr[i].dW, arr[i].n = W.data_ptr(), dW.data_ptr(), W.numel()
-            arr[i].elem0, arr[i].offset = int(elem0), int(offset) & _U64
-        check(lib().hdp_merge_group_sr(len(triples), arr, int(seed) & _U64, _stream()), "hdp_merge_group_sr")
+            rows.append(item + (int(elem0), int(offset) & _U64))
+        arr = (MergeSrItem * len(rows))(*rows)
+        check(lib().hdp_merge_group_sr(len(rows), arr, int(seed) & _U64, _stream()), "hdp_merge_group_sr")
 
     def copy_group(self, pairs) -> None:
         """dst <- src for many contiguous (dst, src) pairs of equal byte size (any dtypes) in one launch
@@ -407,14 +412,12 @@ class HipOps:
         from ._lib import CopyItem
         if not pairs:
             return
-        arr = (CopyItem * len(pairs))()
-        for i, (dst, src) in enumerate(pairs):
+        rows = []
+        for dst, src in pairs:
             _need_gpu(dst, src)
-            nb = dst.numel() * dst.element_size()
-            if nb != src.numel() * src.element_size() or not dst.is_contiguous() or not src.is_contiguous():
-                raise ValueError("copy_group: dst and src must be contiguous with equal byte sizes")
-            arr[i].dst, arr[i].src, arr[i].bytes = dst.data_ptr(), src.data_ptr(), nb
-        check(lib().hdp_copy_group(len(pairs), arr, _stream()), "hdp_copy_group")
+            rows.append(_stream_pair("copy_group", "dst", "src", dst, src, src_f32=False, in_bytes=True))
+        arr = (CopyItem * len(rows))(*rows)
+        check(lib().hdp_copy_group(len(rows), arr, _stream()), "hdp_copy_group")
 
     def shadow_group(self, pairs) -> None:
         """dst <- bf16(src), round to nearest even, for many contiguous ``(dst bfloat16, src float32)`` pairs of
@@ -423,16 +426,12 @@ class HipOps:
         from ._lib import ShadowItem
         if not pairs:
             return
-        arr = (ShadowItem * len(pairs))()
-        for i, (dst, src) in enumerate(pairs):
+        rows = []
+        for dst, src in pairs:
             _need_gpu(dst, src)
-            _f32(src)
-            if dst.dtype != torch.bfloat16:
-                raise TypeError(f"shadow_group: dst must be bfloat16, got {dst.dtype}")
-            if dst.numel() != src.numel() or not dst.is_contiguous() or not src.is_contiguous():
-                raise ValueError("shadow_group: dst and src must be contiguous with equal sizes")
-            arr[i].dst, arr[i].src, arr[i].n = dst.data_ptr(), src.data_ptr(), dst.numel()
-        check(lib().hdp_shadow_group(len(pairs), arr, _stream()), "hdp_shadow_group")
+            rows.append(_stream_pair("shadow_group", "dst", "src", dst, src, dst_bf16=True))
+        arr = (ShadowItem * len(rows))(*rows)
+        check(lib().hdp_shadow_group(len(rows), arr, _stream()), "hdp_shadow_group")
 
     def fold_bf16(self, parts: torch.Tensor, out: torch.Tensor) -> None:
         """Rank-ordered bf16 fold (hp:389-392 rounding order): parts [nparts, n] float32 (rank i's

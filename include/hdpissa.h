@@ -66,7 +66,8 @@ int hdp_merge(void* W, int w_dtype, const float* dW, int64_t n, void* stream);
 
 /* Grouped K5: every module of one exchange bucket in one launch (W_i += dW_i, same semantics as
  * hdp_merge per item; items that are not 16-B aligned or a whole number of vectors fall back to
- * hdp_merge).  items is a HOST array read during the call. */
+ * hdp_merge).  items is a HOST array read during the call; n < 0 or a null pointer with n > 0 is
+ * HDP_EINVAL before anything is launched. */
 typedef struct {
   void* W;          /* n elements, w_dtype */
   const float* dW;  /* n float32 */
