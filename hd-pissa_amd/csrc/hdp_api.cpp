@@ -29,7 +29,7 @@ static const char* const kKernelNames[K_COUNT] = {
     "merge", "adam", "delta_gemm", "delta_gemm_multiseg", "probe_p1", "probe_p2", "probe_finish", "probe_reduce",
     "probe_sweep_a", "probe_sweep_b", "probe_sweep_c", "svd_gemm", "delta_pack", "fold_bf16",
     "probe_dropout", "probe_dropout_finish", "copy_group", "grad_sumsq", "clip_finish",
-    "merge_sr", "shadow_group"};
+    "merge_sr", "shadow_group", "merge_comp"};
 struct TimingRec {
   int kid;
   hipEvent_t a, b;

@@ -5,6 +5,7 @@
 //   merge bf16 W:  8 B/element (read W 2, read dW 4, write W 2)
 //   adam        : 24 B/element (read g, m, v; write m, v, delta) (+4 with zero_grad)
 #include "hdp_common.h"
+#include "hdp_comp.h"
 #include "hdp_sr.h"
 #include "hdp_stream_plan.h"
 
@@ -181,8 +182,9 @@ __global__ void merge_scalar_kernel(void* W, int dt, const float* dW, int64_t be
 }
 
 // ---------------------------------------------------------------------------------------
-// The grouped stream kernels behind one walk: the stochastic-rounding merge of hdp_sr.h, the grouped copy of
-// the shard exchange's pack and scatter, and the float32 -> bf16 cast of the compute copies (compute_dtype=).
+// The grouped stream kernels behind one walk: the stochastic-rounding merge of hdp_sr.h, the compensated merge of
+// hdp_comp.h, the grouped copy of the shard exchange's pack and scatter, and the float32 -> bf16 cast of the
+// compute copies (compute_dtype=).
 // (The round-to-nearest merges above keep their own kernels: through this walk they measured 2-6 % slower,
 // DESIGN section 5.)  stream_group_kernel<Op>:
 //   * one flat chunk space over a launch's items; a workgroup walks chunks blockIdx.x, + grid, ... and owns
@@ -256,6 +258,60 @@ struct MergeSrOp : MergeSrPlan {
           o[k] = sr_round(__float_as_uint(s0), rb.w[k] & 0xFFFFu) | (sr_round(__float_as_uint(s1), rb.w[k] >> 16) << 16);
         }
         __builtin_nontemporal_store(__builtin_bit_cast(u16x8, o), W8 + i);
+      }
+    }
+  }
+};
+
+// bf16 (W, C) <- the compensated merge of float32 dW (contract in hdp_comp.h), 12 B per element: a vector is two
+// 16-byte dW loads, one W load and one C load, then one W store and one C store
+struct MergeCompOp : MergeCompPlan {
+  struct Elem {
+    uint16_t w, c;
+    float d;
+  };
+  HDP_OP_FN Elem load1(const Item& it, int64_t j) {
+    return Elem{gptr_as<uint16_t>(it.W)[j], gptr_as<uint16_t>(it.C)[j], gptr(it.dW)[j]};
+  }
+  HDP_OP_FN void store1(const Item& it, const NoKey&, int64_t j, const Elem& e) {
+    const CompPair o = comp_merge1(e.w, e.c, e.d);
+    gptr_as<uint16_t>(it.W)[j] = static_cast<uint16_t>(o.w);
+    gptr_as<uint16_t>(it.C)[j] = static_cast<uint16_t>(o.c);
+  }
+  HDP_OP_FN void vec_chunk(const Item& it, const NoKey&, const StreamSplit& sp, int64_t v0) {
+    constexpr int U = kU;
+    const int64_t nv = sp.nv;
+    const HDP_GLOBAL f32x4* D4 = gptr_as<f32x4>(it.dW);
+    HDP_GLOBAL u32x4* W8 = gptr_as<u32x4>(it.W);
+    HDP_GLOBAL u32x4* C8 = gptr_as<u32x4>(it.C);
+    u32x4 w[U], cc[U];
+    f32x4 d0[U], d1[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = v0 + u * kEwThreads;
+      if (i < nv) {
+        d0[u] = __builtin_nontemporal_load(D4 + 2 * i);
+        d1[u] = __builtin_nontemporal_load(D4 + 2 * i + 1);
+        w[u] = __builtin_nontemporal_load(W8 + i);
+        cc[u] = __builtin_nontemporal_load(C8 + i);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t i = v0 + u * kEwThreads;
+      if (i < nv) {
+        u32x4 ow, oc;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {  // word k: elements 2k (low halves) and 2k + 1 (high halves)
+          const f32x4& dd = k < 2 ? d0[u] : d1[u];
+          const CompPair lo = comp_merge_f(__uint_as_float(w[u][k] << 16), __uint_as_float(cc[u][k] << 16), dd[(2 * k) & 3]);
+          const CompPair hi = comp_merge_f(__uint_as_float(w[u][k] & 0xffff0000u), __uint_as_float(cc[u][k] & 0xffff0000u),
+                                           dd[(2 * k + 1) & 3]);
+          ow[k] = lo.w | (hi.w << 16);
+          oc[k] = lo.c | (hi.c << 16);
+        }
+        __builtin_nontemporal_store(ow, W8 + i);
+        __builtin_nontemporal_store(oc, C8 + i);
       }
     }
   }
@@ -742,6 +798,10 @@ extern "C" int hdp_merge_group_bf16dw(int n, const hdp_merge_item* items, void* 
 extern "C" int hdp_merge_group_sr(int n, const hdp_merge_sr_item* items, uint64_t seed, void* stream) {
   const SrSeed key{static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32)};
   return stream_group_run<MergeSrOp>("hdp_merge_group_sr", K_MERGE_SR, n, items, key, stream);
+}
+
+extern "C" int hdp_merge_group_comp(int n, const hdp_merge_comp_item* items, void* stream) {
+  return stream_group_run<MergeCompOp>("hdp_merge_group_comp", K_MERGE_COMP, n, items, NoKey{}, stream);
 }
 
 extern "C" int hdp_copy_group(int n, const hdp_copy_item* items, void* stream) {

@@ -1,5 +1,5 @@
 // Host plan of the grouped HBM-streaming kernels that share one chunk walk (hdp_elementwise.hip: the
-// stochastic-rounding merge, the grouped copy and the float32 -> bf16 shadow cast): how one item splits into
+// stochastic-rounding merge, the compensated merge, the grouped copy and the float32 -> bf16 shadow cast): how one item splits into
 // vector, edge and element-wise work, the validation of one item, and the batcher that cuts an item list into launches.  Pure C++ (no HIP, no environment):
 // hipcc and the host compiler build the same code, the kernel calls the same split the host sums chunks
 // with, and tests/stream_plan_check.cpp walks it on the CPU (tests/test_stream_plan.py, plain and under
@@ -124,6 +124,25 @@ struct ShadowPlan {
   }
 };
 
+// bf16 (W, C) <- compensated merge of float32 dW (hdp_comp.h): vectors when W, C and dW are all 16-byte aligned
+struct MergeCompPlan {
+  using Item = hdp_merge_comp_item;
+  using Key = NoKey;
+  static constexpr int kCap = 127, kU = 4, kVec = 8, kElemU = 4;
+  static constexpr double kBytes = 12;  // read W 2, C 2, dW 4; write W 2, C 2
+  static HDP_SP_HD int64_t count(const Item& it) { return it.n; }
+  static HDP_SP_HD StreamSplit split(const Item& it) {
+    return stream_split<MergeCompPlan>(stream_aligned16(it.W, it.C) && stream_aligned16(it.dW, it.dW), 0, it.n);
+  }
+  static const char* check(const Item& it) {
+    if (it.n < 0) return " has n < 0";
+    if (it.n && !(it.W && it.C && it.dW)) return " has a null pointer";
+    if (it.n && (((stream_addr(it.W) | stream_addr(it.C)) & 1u) || (stream_addr(it.dW) & 3u)))
+      return ": W and C must be 2-byte and dW 4-byte aligned";
+    return nullptr;
+  }
+};
+
 // ---- one launch's kernel arguments: the items by value (the 4 KB kernel-argument block sets the caps)
 template <class P>
 struct StreamArgs {
@@ -132,7 +151,7 @@ struct StreamArgs {
   typename P::Item it[P::kCap];
 };
 static_assert(sizeof(StreamArgs<MergeSrPlan>) <= 4096 && sizeof(StreamArgs<CopyPlan>) <= 4096 &&
-                  sizeof(StreamArgs<ShadowPlan>) <= 4096,
+                  sizeof(StreamArgs<ShadowPlan>) <= 4096 && sizeof(StreamArgs<MergeCompPlan>) <= 4096,
               "stream kernel arguments must stay within 4 KB");
 
 // ---- the batcher

@@ -47,6 +47,11 @@ class MergeSrItem(ctypes.Structure):
                 ("offset", ctypes.c_uint64)]
 
 
+class MergeCompItem(ctypes.Structure):
+    """hdp_merge_comp_item (include/hdpissa.h)."""
+    _fields_ = [("W", ctypes.c_void_p), ("C", ctypes.c_void_p), ("dW", ctypes.c_void_p), ("n", ctypes.c_int64)]
+
+
 class CopyItem(ctypes.Structure):
     """hdp_copy_item (include/hdpissa.h)."""
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
@@ -78,6 +83,8 @@ def clip_record(raw) -> dict:
 COPY_GROUP_MAX = 170 # non-empty items per launch of hdp_copy_group (its kernel-argument block)
 SHADOW_GROUP_MAX = 170  # non-empty items per launch of hdp_shadow_group (its kernel-argument block)
 SHADOW_CHUNK = 256 * 8 * 8  # elements one workgroup of hdp_shadow_group casts at a time
+MERGE_COMP_MAX = 127  # non-empty items per launch of hdp_merge_group_comp (its kernel-argument block)
+MERGE_COMP_CHUNK = 256 * 4 * 8  # elements one workgroup of hdp_merge_group_comp merges at a time
 
 
 class SvdItem(ctypes.Structure):
@@ -102,6 +109,7 @@ SIGNATURES = {
     "hdp_merge_group": (_c_int, [_c_int, ctypes.POINTER(MergeItem), _c_int, _c_vp]),
     "hdp_merge_group_bf16dw": (_c_int, [_c_int, ctypes.POINTER(MergeItem), _c_vp]),
     "hdp_merge_group_sr": (_c_int, [_c_int, ctypes.POINTER(MergeSrItem), ctypes.c_uint64, _c_vp]),
+    "hdp_merge_group_comp": (_c_int, [_c_int, ctypes.POINTER(MergeCompItem), _c_vp]),
     "hdp_fold_bf16": (_c_int, [_c_vp, _c_int, _c_i64, _c_vp, _c_i64, _c_vp]),
     "hdp_copy_group": (_c_int, [_c_int, ctypes.POINTER(CopyItem), _c_vp]),
     "hdp_shadow_group": (_c_int, [_c_int, ctypes.POINTER(ShadowItem), _c_vp]),

@@ -51,7 +51,8 @@ def save_hdpissa_state(model: nn.Module, path: str, t: int) -> None:
     """Everything an HD-PiSSA run needs to resume at an optimizer-step boundary, one safetensors
     file per rank: every rank's factors (fac_all: A, B are frozen after init, hp:375-376), this
     rank's Adam moments m, v and pending gradients, the merged weights W_res (they change every
-    step, hp:394) and the step counter t (hp:300, 350).  Metadata records the module layout
+    step, hp:394), for layers that carry one the compensation term W_c (merge_rounding="compensated"; a file
+    written with the mode off has no such tensor) and the step counter t (hp:300, 350).  Metadata records the module layout
     (names, shapes, r, arena offsets, and whether the layer stores the PiSSA residual -- there
     W_res = W - sum B_i A_i, so the same W_res means a different effective weight) so
     load_hdpissa_state refuses a mismatched model."""
@@ -67,6 +68,9 @@ def save_hdpissa_state(model: nn.Module, path: str, t: int) -> None:
         for L, (oa, ob) in zip(a.layers, a.offsets):
             n = names[id(L)]
             tensors[f"{n}.W_res"] = L.W_res.detach().contiguous().cpu()
+            c = L._compensation()  # merge_rounding="compensated": the compensation term (None: mode off)
+            if c is not None:
+                tensors[f"{n}.W_c"] = c.detach().contiguous().cpu()
             mods.append([n, L.out_features, L.in_features, L.r, oa, ob, bool(L.residual)])
         layout.append({"world_size": a.world_size, "rank": a.rank, "F": a.F, "modules": mods})
     meta["layout"] = json.dumps(layout)
@@ -85,6 +89,7 @@ def load_hdpissa_state(model: nn.Module, path: str) -> int:
         if meta.get("format") != "hdpissa-resume-1":
             raise ValueError(f"{path}: not an HD-PiSSA resume file")
         layout = json.loads(meta["layout"])
+        keys = set(f.keys())
         arenas = _arenas(model)
         if len(layout) != len(arenas):
             raise ValueError("resume file and model have different adapter arenas")
@@ -100,6 +105,11 @@ def load_hdpissa_state(model: nn.Module, path: str) -> int:
                     getattr(a, k).copy_(f.get_tensor(f"arena{ai}.{k}"))
                 for L in a.layers:
                     L.W_res.copy_(f.get_tensor(f"{names[id(L)]}.W_res"))
+                    if f"{names[id(L)]}.W_c" in keys:  # written under merge_rounding="compensated"
+                        L.enable_compensation().copy_(f.get_tensor(f"{names[id(L)]}.W_c"))
+                        L._comp_version = L.W_res._version  # (after both copies)
+                    else:
+                        L.reset_compensation()  # (a no-op without a buffer)
                     if L.residual:  # the forward's x A_all^T B_cat^T must use the restored factors
                         _bind_residual_factors(L)
         return int(meta["t"])

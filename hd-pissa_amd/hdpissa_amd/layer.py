@@ -30,6 +30,10 @@ What changes underneath (MI355X-native):
     checkpoints are unchanged) holds bf16(W_res); the base GEMMs of forward and backward read it -- y and
     dX are bf16 GEMMs on bf16(x) -- and the probe takes the bf16 activations through its bf16 paths, while
     the step keeps merging into the float32 W_res and refreshes the copy (``refresh_shadow``, HDPissaStep).
+  * merge_rounding="compensated" on the stepper (opt-in): a bf16 W_res carries ``layer.W_c``, a bf16
+    compensation term of its shape (a non-persistent buffer: checkpoints are unchanged; None while the mode
+    is off) -- ``enable_compensation`` / ``reset_compensation``; the step zeroes it by itself when W_res's
+    version counter moved, and ``save_hdpissa_state`` / ``load_hdpissa_state`` carry it.
 """
 from __future__ import annotations
 
@@ -414,6 +418,10 @@ class CustomLinearLayer(nn.Module):
                              persistent=False)
         self._shadow_version = None
         self._bias_lp, self._bias_lp_version = None, None
+        # merge_rounding="compensated": W_c, the bf16 compensation term of a bf16 W_res (enable_compensation);
+        # not in the state dict.  None while the mode is off
+        self.register_buffer("W_c", None, persistent=False)
+        self._comp_version = None
         if shadow:
             self.refresh_shadow()
         self._arena: Optional[FactorArena] = None
@@ -486,6 +494,49 @@ class CustomLinearLayer(nn.Module):
         if self._shadow_version != W._version:
             self.refresh_shadow()
         return lp
+
+    # -- merge_rounding="compensated": the bf16 compensation term of a bf16 W_res -------------
+    def enable_compensation(self) -> torch.Tensor:
+        """W_c: zeros of W_res's shape (bf16), the compensation term the compensated merge carries beside a
+        bf16 W_res (HDPissaStep(merge_rounding="compensated") calls this).  An existing buffer that still
+        matches W_res is kept as it is, so rebuilding a stepper does not lose the state."""
+        bufs = self._buffers
+        W, c = bufs["W_res"], bufs.get("W_c")
+        if W.dtype != torch.bfloat16:
+            raise TypeError(f"{self.name}: the compensated merge needs a bfloat16 W_res, got {W.dtype}")
+        if c is None or c.dtype != torch.bfloat16 or c.shape != W.shape or c.device != W.device:
+            self.W_c = c = torch.zeros_like(W, memory_format=torch.contiguous_format)
+            self._comp_version = W._version
+        return c
+
+    def reset_compensation(self) -> None:
+        """W_c <- 0 on the current stream (W_res was rewritten: what W_c held back belongs to the old weight).
+        The step does this itself when W_res's version counter moved (``copy_``, ``load_state_dict``,
+        ``make_residual``); after a write the counter does not see (``.data``, raw pointers) the caller calls
+        it.  A no-op without a buffer."""
+        bufs = self._buffers
+        c = bufs.get("W_c")
+        if c is None:
+            return
+        with torch.no_grad():
+            c.zero_()
+        self._comp_version = bufs["W_res"]._version
+
+    def _compensation(self) -> Optional[torch.Tensor]:
+        """The compensation term the next merge reads, or None if the layer keeps none: zeroed first if W_res
+        was written since W_c was last made consistent with it.  A W_res that is no longer bf16 (or that
+        changed shape or device) drops the buffer."""
+        bufs = self._buffers
+        c = bufs.get("W_c")
+        if c is None:
+            return None
+        W = bufs["W_res"]
+        if W.dtype != torch.bfloat16 or c.dtype != torch.bfloat16 or c.shape != W.shape or c.device != W.device:
+            self.W_c, self._comp_version = None, None
+            return None
+        if self._comp_version != W._version:
+            self.reset_compensation()
+        return c
 
     def _bias_shadow(self) -> Optional[torch.Tensor]:
         """bf16(bias), cast once and again when the bias is written."""
@@ -743,8 +794,9 @@ def make_residual(layers: Sequence["CustomLinearLayer"]) -> None:
             else:
                 for it in group:
                     ops.delta_gemm(*it, HDP_DW_MERGE, False)
-    for L in layers:  # K4 wrote W_res through its pointer: the bf16 copies follow
+    for L in layers:  # K4 wrote W_res through its pointer: the bf16 copies follow, a compensation term restarts
         L.refresh_shadow()
+        L.reset_compensation()
 
 
 def replace_with_custom_layer(model: nn.Module, target_modules: Sequence[str], rank: int, world_size: int,

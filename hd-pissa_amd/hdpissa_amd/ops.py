@@ -53,7 +53,7 @@ def _clip_ptr(state: torch.Tensor) -> int:
 
 
 def _stream_pair(what: str, a: str, b: str, dst, src, dst_bf16=False, src_f32=True, in_bytes=False):
-    """One (dst, src) pair of a grouped stream op (merge_group, merge_group_sr, copy_group, shadow_group): of the
+    """One (dst, src) pair of a grouped stream op (merge_group, merge_group_sr, merge_group_comp, copy_group, shadow_group): of the
     dtypes the op takes, contiguous and of equal size (the caller has checked the device).  Returns (dst pointer, src pointer, count),
     the count in elements, or in bytes for the copy.  ``a`` / ``b`` are the op's names for dst and src."""
     if src_f32:
@@ -405,6 +405,22 @@ class HipOps:
             rows.append(item + (int(elem0), int(offset) & _U64))
         arr = (MergeSrItem * len(rows))(*rows)
         check(lib().hdp_merge_group_sr(len(rows), arr, int(seed) & _U64, _stream()), "hdp_merge_group_sr")
+
+    def merge_group_comp(self, triples) -> None:
+        """Compensated merge over many ``(W, C, dW)`` items (one exchange bucket): bfloat16 W and its bfloat16
+        compensation term C take the float32 dW as s = (C + dW) + W, W = bf16(s), C = bf16(s - W)
+        (hdp_merge_group_comp; the contract and its numpy replica: hdpissa_amd.rounding.comp_merge_bits)."""
+        from ._lib import MergeCompItem
+        if not triples:
+            return
+        rows = []
+        for W, C, dW in triples:
+            _need_gpu(W, C, dW)
+            pw, pd, n = _stream_pair("merge_group_comp", "W", "dW", W, dW, dst_bf16=True)
+            pc, _, _ = _stream_pair("merge_group_comp", "C", "dW", C, dW, dst_bf16=True)
+            rows.append((pw, pc, pd, n))
+        arr = (MergeCompItem * len(rows))(*rows)
+        check(lib().hdp_merge_group_comp(len(rows), arr, _stream()), "hdp_merge_group_comp")
 
     def copy_group(self, pairs) -> None:
         """dst <- src for many contiguous (dst, src) pairs of equal byte size (any dtypes) in one launch

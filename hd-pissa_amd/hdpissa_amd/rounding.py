@@ -1,5 +1,6 @@
-"""Host replica of the stochastic-rounding merge contract (numpy only; DESIGN.md 2.2, kernel
-``csrc/hdp_sr.h`` / ``hdp_merge_group_sr``).
+"""Host replicas of the two opt-in bf16 merge contracts (numpy only): the stochastic-rounding merge (DESIGN.md
+2.2, kernel ``csrc/hdp_sr.h`` / ``hdp_merge_group_sr``) and, at the end of the module, the compensated merge
+(``csrc/hdp_comp.h`` / ``hdp_merge_group_comp``).
 
 With ``merge_rounding="stochastic"`` a bf16 W takes its update as ``W = sr(float32(W) + dW)``.  For element
 ``e = o * in + i`` (64-bit) of the module's W:
@@ -86,3 +87,47 @@ def sr_merge_reference(W, dW, elem0: int, seed: int, offset: int):
     d = dW.detach().contiguous().cpu().float().numpy().reshape(bits.shape)
     out = sr_merge_bits(bits, d, elem0, seed, offset)
     return torch.from_numpy(out.view(np.int16).copy()).view(torch.bfloat16).view(W.shape)
+
+
+# ---- merge_rounding="compensated": a bf16 W with a bf16 compensation term C (Kahan summation) -------------
+# For one element, w and c the bf16 bits read as float32 by << 16, dW float32:
+#   a  = float32(c) + dW             one IEEE float32 add (c and dW are both small against w: added first, their
+#                                    sum keeps bits that either would lose against w)
+#   s  = a + float32(w)              one IEEE float32 add
+#   w' = rne_bf16(s)                 inf stays inf, NaN stays quiet NaN, a carry at the top gives inf
+#   c' = rne_bf16(s - float32(w'))   if s and float32(w') are both finite (the difference is exact in float32)
+#   c' = +0.0                        otherwise
+# No random bits and no dependence on the element's index, the rank, the bucket or the launch.
+def comp_merge_bits(w_bits, c_bits, dW):
+    """``w_bits`` / ``c_bits``: the bf16 bits (uint16) of W and of its compensation term, ``dW`` their float32
+    updates -> ``(w_bits', c_bits')`` (uint16 arrays of the shape of ``w_bits``)."""
+    w_bits = np.asarray(w_bits, dtype=np.uint16)
+    c_bits = np.asarray(c_bits, dtype=np.uint16).reshape(w_bits.shape)
+    dW = np.asarray(dW, dtype=np.float32).reshape(w_bits.shape)
+    w = (w_bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
+    c = (c_bits.astype(np.uint32) << np.uint32(16)).view(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        a = (c + dW).astype(np.float32)
+        s = (a + w).astype(np.float32)
+        wo = rne_bf16_bits(s.view(np.uint32))
+        res = (s - (wo << np.uint32(16)).view(np.float32)).astype(np.float32)
+    finite = (wo & np.uint32(0x7F80)) != np.uint32(0x7F80)  # (s not finite -> w' not finite)
+    co = np.where(finite, rne_bf16_bits(res.view(np.uint32)), np.uint32(0))
+    return wo.astype(np.uint16), co.astype(np.uint16)
+
+
+def comp_merge_reference(W, C, dW):
+    """The same on bfloat16 torch tensors ``W`` and ``C`` (any device; returns new host tensors of W's shape)."""
+    import torch
+
+    def bits(t):
+        return t.detach().contiguous().cpu().view(torch.int16).numpy().view(np.uint16)
+
+    wb = bits(W)
+    d = dW.detach().contiguous().cpu().float().numpy().reshape(wb.shape)
+    wo, co = comp_merge_bits(wb, bits(C).reshape(wb.shape), d)
+
+    def back(b):
+        return torch.from_numpy(b.view(np.int16).copy()).view(torch.bfloat16).view(W.shape)
+
+    return back(wo), back(co)

@@ -50,6 +50,17 @@ float32 all-reduce instead of the rank-ordered fold.  The random bits depend on 
 only, so every rank -- and under "shard" whichever rank merges a row -- writes the same W.  float32 modules
 take exactly the launches they always took.
 
+Opt-in, off by default (``merge_rounding="compensated"``; the reference rounds to nearest): a bf16 W carries a
+bf16 compensation term ``layer.W_c`` of its shape (Kahan summation) and takes its update as s = (W_c + dW) + W,
+W = bf16(s), W_c = bf16(s - W) (hdpissa_amd.rounding has the contract and its numpy replica): 4 B per element,
+the base GEMMs read W_res as it is, and the update is kept to about 16 mantissa bits instead of 8.  The step is
+the stochastic mode's with one hdp_merge_group_comp per bucket in place of hdp_merge_group_sr: K3, STORE plans
+into the float32 buckets, the merge on the same stream; under "allreduce" the plain float32 all-reduce; under
+"shard" the rank merges its row blocks of W with the same rows of W_c, and the bucket's pack, all-gather and
+scatter carry the W_c rows beside the W rows -- so W_res and W_c are bitwise equal on all ranks under every
+exchange.  A W_c whose W_res was written since the last merge (its version counter moved) is zeroed in front
+of its merge.  ``sr_seed`` is ignored.  float32 modules take exactly the launches they always took.
+
 Opt-in, off by default (``compute_dtype=torch.bfloat16`` on the layers; the reference computes in the precision
 it stores): float32 master weights with a bf16 compute copy.  When ``step()`` returns, every layer that keeps a
 copy has W_lp == bf16(W_res) element for element, in stream order on the current stream, on every rank, under
@@ -113,27 +124,36 @@ def shard_item(item, Wn: int, k: int):
 class _ShardBucket:
     """One W bucket of the shard exchange: modules [a, b) of one dtype; per module the byte offset of
     its slot in a rank's shard (16-byte aligned, ``block * in`` elements long on every rank, whatever
-    rows the rank really owns) and the shard's length ``nbytes`` (equal on all ranks)."""
+    rows the rank really owns) and the shard's length ``nbytes`` (equal on all ranks).  ``comp``
+    (merge_rounding="compensated"): a bf16 module has a second slot of the same length, ``cslots``, for the
+    same rows of its compensation term W_c (None for the other modules)."""
 
-    def __init__(self, layers, a: int, b: int, Wn: int):
+    def __init__(self, layers, a: int, b: int, Wn: int, comp: bool = False):
         self.a, self.b = a, b
-        self.slots, off = [], 0
+        self.slots, self.cslots, off = [], [], 0
         for L in layers[a:b]:
             self.slots.append(off)
             block = shard_rows(L.out_features, Wn, 0)[1]
-            off += -(-block * L.in_features * L.W_res.element_size() // 16) * 16
+            size = -(-block * L.in_features * L.W_res.element_size() // 16) * 16
+            off += size
+            self.cslots.append(off if comp and L.W_res.dtype == torch.bfloat16 else None)
+            if self.cslots[-1] is not None:
+                off += size
         self.nbytes = off
         self.views = None  # (W_res pointers, dsts, owners, pack, scatter), built on first use (_shard_views)
 
 
 class _ArenaPlan:
     def __init__(self, arena: FactorArena, exchange: str, bucket_bytes: int, sr: bool = False,
-                 sr_bytes: int = 1 << 30):
+                 sr_bytes: int = 1 << 30, comp: bool = False):
         self.arena = arena
         # merge_rounding="stochastic": the bf16 modules' float32 dW goes through HBM -- gather / shard: two
         # buffers of at most ``sr_bytes`` of dense float32 dW (the all-reduce leg's layout; a module above
         # the bound has a bucket of its own); allreduce: its own dw_bufs, summed by the plain all-reduce
+        # (merge_rounding="compensated" runs the same plans and buffers: ``sr`` is set for it too, ``comp``
+        # says which merge follows the STORE)
         self.sr = sr and any(L.W_res.dtype == torch.bfloat16 for L in arena.layers)
+        self.comp = comp and self.sr
         self.sr_cap = max(1, sr_bytes // 4)
         self.sr_bufs: List[torch.Tensor] = []
         self.sr_turn = 0
@@ -191,7 +211,7 @@ class _ArenaPlan:
         for i in range(1, n + 1):
             if i == n or layers[i].W_res.dtype != layers[run].W_res.dtype:
                 sizes = [L.W_res.numel() * L.W_res.element_size() for L in layers[run:i]]
-                self.s_buckets += [_ShardBucket(layers, run + a, run + b, Wn)
+                self.s_buckets += [_ShardBucket(layers, run + a, run + b, Wn, self.comp)
                                    for a, b in _buckets(sizes, max(1, bucket_bytes))]
                 run = i
         cap = max(sb.nbytes for sb in self.s_buckets)
@@ -319,7 +339,7 @@ def _copy_pairs(pairs) -> None:
 
 
 def _sr_seed(merge_rounding: str, sr_seed: Optional[int]) -> Optional[int]:
-    """The seed a stepper runs with: None under "nearest", else ``sr_seed`` as an unsigned 64-bit value
+    """The seed a stepper runs with: None under "nearest" and "compensated" (no random bits), else ``sr_seed`` as an unsigned 64-bit value
     (default: derived from torch's initial seed)."""
     if merge_rounding != "stochastic":
         return None
@@ -336,8 +356,8 @@ class HDPissaStep:
                  merge_rounding: str = "nearest", sr_seed: Optional[int] = None):
         if exchange not in ("gather", "allreduce", "shard"):
             raise ValueError("exchange must be 'gather', 'allreduce' or 'shard'")
-        if merge_rounding not in ("nearest", "stochastic"):
-            raise ValueError("merge_rounding must be 'nearest' or 'stochastic'")
+        if merge_rounding not in ("nearest", "stochastic", "compensated"):
+            raise ValueError("merge_rounding must be 'nearest', 'stochastic' or 'compensated'")
         self.layers = [m for _, m in custom_layers(model)]
         if not self.layers:
             raise ValueError("model has no CustomLinearLayer")
@@ -372,8 +392,18 @@ class HDPissaStep:
         if merge_rounding == "stochastic" and not hasattr(ops, "merge_group_sr"):
             raise NotImplementedError(f"the op set {getattr(ops, 'name', ops)!r} has no merge_group_sr: "
                                       "merge_rounding='stochastic' needs the stochastic-rounding merge kernel")
-        self.plans = [_ArenaPlan(a, exchange, bucket_bytes, merge_rounding == "stochastic", sr_bytes)
-                      for a in arenas.values()]
+        if merge_rounding == "compensated" and not hasattr(ops, "merge_group_comp"):
+            raise NotImplementedError(f"the op set {getattr(ops, 'name', ops)!r} has no merge_group_comp: "
+                                      "merge_rounding='compensated' needs the compensated merge kernel")
+        # the merge that follows a bf16 bucket's STORE under "stochastic" / "compensated" (never called under
+        # "nearest"); compensated: every bf16 layer carries W_c from here on (an existing one is kept)
+        self._merge_bf16 = self._merge_comp if merge_rounding == "compensated" else self._merge_sr
+        if merge_rounding == "compensated":
+            for L in self.layers:
+                if L.W_res.dtype == torch.bfloat16:
+                    L.enable_compensation()
+        self.plans = [_ArenaPlan(a, exchange, bucket_bytes, merge_rounding != "nearest", sr_bytes,
+                                 merge_rounding == "compensated") for a in arenas.values()]
         if comm is None:  # the arena's init communicator (module-sharded SVD) if it has one
             comm = next((p.arena.comm for p in self.plans if getattr(p.arena, "comm", None) is not None), None)
         if comm is None:
@@ -494,7 +524,8 @@ class HDPissaStep:
             self._collect_grads(arena)
         self._t = t
         plan.sr_turn = 0
-        # (stochastic rounding merges from the float32 dW: no MERGE epilogue, so no fused Adam-pack either)
+        # (stochastic rounding and the compensated merge work from the float32 dW: no MERGE epilogue, so no
+        # fused Adam-pack either)
         fused = None if plan.sr else self._fused_plans(plan, lr, t)
         if fused is not None:
             # K3 folded into K4's operand preparation -- per plan one Adam pass that also
@@ -512,6 +543,10 @@ class HDPissaStep:
             self._shard(plan)
         else:
             self._allreduce(plan)
+        if plan.comp:  # W_c is consistent with the W_res this step wrote (whatever counted the writes)
+            for L in arena.layers:
+                if L._buffers.get("W_c") is not None:
+                    L._comp_version = L._buffers["W_res"]._version
 
     def _fused_plans(self, plan: _ArenaPlan, lr: float, t: int):
         """The Wn = 1 gather plans when every one of them folds Adam in (single-segment H2 merges:
@@ -571,7 +606,7 @@ class HDPissaStep:
         for L, (_, W) in zip(sh, pairs):
             L._shadow_version = W._version
 
-    # -- merge_rounding = "stochastic" ---------------------------------------------------
+    # -- merge_rounding = "stochastic" / "compensated" -----------------------------------
     def _sr_offset(self, L) -> int:
         from .rounding import sr_offset
         return sr_offset(self._layer_index[id(L)], self._t)
@@ -581,13 +616,25 @@ class HDPissaStep:
         element in its W, layer)`` entries: the layer gives the module's Philox offset of this step."""
         self.ops.merge_group_sr([(W, dW, e0, self._sr_offset(L)) for W, dW, e0, L in entries], self.sr_seed)
 
+    def _merge_comp(self, entries) -> None:
+        """merge_rounding="compensated": one merge_group_comp on the current stream over the same entries --
+        the rows of the layer's W_c that lie where the W rows lie in W_res ride along; a W_c whose W_res was
+        written since it was last made consistent is zeroed first, on this stream."""
+        triples = []
+        for W, dW, e0, L in entries:
+            C = L._compensation()
+            if C is None:  # (the buffer was taken away since the constructor made it)
+                C = L.enable_compensation()
+            triples.append((W, C.view(-1)[e0:e0 + W.numel()].view(W.shape), dW))
+        self.ops.merge_group_comp(triples)
+
     def _sr_slots(self, src: torch.Tensor, slots) -> list:
         """The all-reduce leg's merge of one bucket under stochastic rounding: the bf16 modules of ``slots``
         ((layer, offset into src, n)) merged by one merge_group_sr on the current stream; returns the other
         (float32) slots for the caller's K5."""
         sr = [(L.W_res, src[o:o + n], 0, L) for L, o, n in slots if L.W_res.dtype == torch.bfloat16]
         if sr:
-            self._merge_sr(sr)
+            self._merge_bf16(sr)
         return [s for s in slots if s[0].W_res.dtype != torch.bfloat16]
 
     def _sr_merge(self, plan: _ArenaPlan, key, make_items, dsts, owners) -> None:
@@ -610,7 +657,7 @@ class HDPissaStep:
             stores = [buf[off:off + n] for off, n, _, _ in slots]
             self._k4(plan, pkey + (plan.sr_turn % 2,), lambda: [it + (s,) for it, s in zip(its, stores)], HDP_DW_STORE,
                      stores)
-            self._merge_sr([(d, s, e0, L) for d, s, (_, _, e0, L) in zip(ds, stores, slots)])
+            self._merge_bf16([(d, s, e0, L) for d, s, (_, _, e0, L) in zip(ds, stores, slots)])
 
     @staticmethod
     def _sr_program(key, items, dsts, owners, cap: int) -> list:
@@ -684,26 +731,29 @@ class HDPissaStep:
         (the K4 destinations) and their layers, and per buffer pair the (dst, src) byte ranges that move them
         into the send buffer and every other rank's rows from the gather buffer into W_res."""
         layers, Wn = plan.arena.layers[sb.a:sb.b], self.world_size
-        ptrs = tuple(L.W_res.data_ptr() for L in layers)
+        comps = [L._buffers.get("W_c") if coff is not None else None for L, coff in zip(layers, sb.cslots)]
+        ptrs = tuple(L.W_res.data_ptr() for L in layers) + tuple(0 if c is None else c.data_ptr() for c in comps)
         if sb.views is not None and sb.views[0] == ptrs:
             return sb.views[1:]
         dsts, owners, pack, scat = [], [], ([], []), ([], [])
-        for L, off in zip(layers, sb.slots):
+        for L, off, coff, comp in zip(layers, sb.slots, sb.cslots, comps):
             row = L.in_features * L.W_res.element_size()
             for j in range(Wn):
                 r0, r1 = shard_rows(L.out_features, Wn, j)
                 if r1 <= r0:
                     continue
-                rows = L.W_res[r0:r1].reshape(-1).view(torch.uint8)
                 if j == self.rank:
                     dsts.append(L.W_res[r0:r1])
                     owners.append(L)
-                for q in range(2):
-                    if j == self.rank:
-                        pack[q].append((plan.s_send[q][off:off + (r1 - r0) * row], rows))
-                    else:
-                        o = j * sb.nbytes + off
-                        scat[q].append((rows, plan.s_gath[q][o:o + (r1 - r0) * row]))
+                # (compensated: the same rows of W_c travel in the module's second slot)
+                for T, at in ((L.W_res, off),) + (((comp, coff),) if comp is not None else ()):
+                    rows = T[r0:r1].reshape(-1).view(torch.uint8)
+                    for q in range(2):
+                        if j == self.rank:
+                            pack[q].append((plan.s_send[q][at:at + (r1 - r0) * row], rows))
+                        else:
+                            o = j * sb.nbytes + at
+                            scat[q].append((rows, plan.s_gath[q][o:o + (r1 - r0) * row]))
         sb.views = (ptrs, dsts, owners, pack, scat)
         return sb.views[1:]
 
@@ -714,6 +764,9 @@ class HDPissaStep:
         for bi, sb in enumerate(plan.s_buckets):
             q = bi % 2
             pipe.wait(events[plan.g_of[sb.b - 1]])  # the delta buckets that cover modules [a, b) (in stream order)
+            if plan.comp:  # (a stale W_c is zeroed here, whether or not this rank merges rows of it)
+                for L in plan.arena.layers[sb.a:sb.b]:
+                    L._compensation()
             dsts, owners, pack, scat = self._shard_views(plan, sb)
             items = lambda sb=sb: self._shard_items(plan, sb, self.rank)  # noqa: E731
             if dsts and plan.sr:
@@ -800,7 +853,8 @@ def hd_pissa_step(model: nn.Module, lr: float, t: int, world_size: int, rank: in
     The step object (plan, buffers, streams) is cached per model.  ``max_grad_norm``: clip the global
     gradient norm and skip non-finite steps on the device (HDPissaStep; None, the default: the reference's
     step).  ``merge_rounding="stochastic"`` (with ``sr_seed``): bf16 weights take the update by stochastic
-    rounding from the float32 sum (HDPissaStep; "nearest", the default: the reference's merge)."""
+    rounding from the float32 sum; ``merge_rounding="compensated"``: bf16 weights carry a bf16 compensation term
+    ``layer.W_c`` (``sr_seed`` is ignored; HDPissaStep; "nearest", the default: the reference's merge)."""
     st = _STEPPERS.get(id(model))
     mgn = None if max_grad_norm is None else float(max_grad_norm)
     seed = _sr_seed(merge_rounding, sr_seed)

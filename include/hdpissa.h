@@ -107,6 +107,30 @@ typedef struct {
 } hdp_merge_sr_item;
 int hdp_merge_group_sr(int n, const hdp_merge_sr_item* items, uint64_t seed, void* stream);
 
+/* Compensated merge (merge_rounding="compensated"; opt-in, the reference has no counterpart): a bfloat16 W
+ * carries a bfloat16 compensation term C of its own shape (Kahan summation) and takes a float32 dW.  For
+ * element j of an item, w = W[j] and c = C[j] read as float32 (bits << 16):
+ *   a    = float32(c) + dW[j]            one IEEE float32 add
+ *   s    = a + float32(w)                one IEEE float32 add
+ *   W[j] = w' = round-to-nearest-even bf16 of s (inf stays inf, NaN stays quiet NaN, a carry at the top gives inf)
+ *   C[j] = round-to-nearest-even bf16 of (s - float32(w'))  if s and float32(w') are both finite
+ *        = +0.0                                             otherwise
+ * s - float32(w') is exact in float32.  No multiplies, subnormals kept, no random bits: the result depends on
+ * (w, c, dW[j]) only, not on the element's index or on the launch.  W and C are bfloat16 only.  Any n >= 0 and
+ * any alignment (W and C 2-byte, dW 4-byte): an item with W, C and dW all 16-byte aligned moves as 8-element
+ * vectors with an element-wise n % 8 tail, any other item element by element, with the same bits; nothing
+ * outside [W, W + n) and [C, C + n) is written.  The W and C ranges of one call must not overlap each other
+ * (not checked).  More than 127 non-empty items are split over launches.  items is a HOST array read during
+ * the call; a bad item is HDP_EINVAL before anything is launched.  csrc/hdp_comp.h holds the function,
+ * hdpissa_amd/rounding.py (comp_merge_bits) its numpy replica. */
+typedef struct {
+  void* W;          /* n bf16 elements */
+  void* C;          /* n bf16 elements: the compensation term */
+  const float* dW;  /* n float32 */
+  int64_t n;
+} hdp_merge_comp_item;
+int hdp_merge_group_comp(int n, const hdp_merge_comp_item* items, void* stream);
+
 /* Rank-ordered bf16 fold -- the rounding order of hp:389-392 for a bfloat16 model:
  *   delta_W_res = zeros_like(W_res) (bf16);  for i in 0..nparts-1:  delta_W_res -= bracket_i
  * i.e. out = 0; out = bf16(out + parts[i]) for i = 0, 1, ... with parts[i] = -bracket_i (float32,
